@@ -1,6 +1,6 @@
 """VideoMamba encoder benchmark on MI355X (BASELINE.json metric).
 
-    python bench.py [--gpus N --steps K --warmup W --batch B]
+    python bench.py [--gpus N --steps K --warmup W --batch B] [--full] [--dump-outputs DIR]
     torchrun --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 ... bench.py --gpus N
 
 Workload (config C3 of BASELINE.json; the metric is quoted on VideoMamba-M 16f 224):
@@ -23,7 +23,13 @@ roofline block is always the scan at the M-16f shape.
 max-over-ranks / JSON-line control flow on the gloo backend (tests/test_sharding_gloo.py
 launches it under torchrun with 2 ranks).
 
-Extra fields: chunk_p50_ms (B=1 chunk latency, HIP-graph replay; chunk_p50_eager_ms the
+A plain run sets up, warms up, times the K steps and prints the headline line (metric, value,
+unit, ms_per_step, config, ...).  --dump-outputs DIR also writes what the last timed step
+returned (x_vis, x_pool, next state; float32, large ones as a fixed seeded sample of rows)
+as DIR/<name>.npy: the inputs are seeded, so two builds run with the same arguments can be
+compared output for output.  Everything below is measured only with --full.
+
+Extra fields (--full): chunk_p50_ms (B=1 chunk latency, HIP-graph replay; chunk_p50_eager_ms the
 eager launch path), b1_kernels (per-stage roofline fractions of one M layer at the B=1
 chunk shape), roofline of the selective-scan kernel
 (HIP-event timed at the bench shape; algorithmic bytes per launch), cpu_baseline (the
@@ -84,9 +90,11 @@ def _args():
     ap.add_argument("--config", default="m16", choices=sorted(CONFIGS))
     ap.add_argument("--p50-chunks", type=int, default=100)
     ap.add_argument("--scan-reps", type=int, default=50)
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--no-cpu-baseline", action="store_true",
+                    help="with --full: skip the CPU baseline leg")
     ap.add_argument("--no-b1", action="store_true",
-                    help="skip the B=1 chunk latency and per-stage B=1 rooflines (batch sweeps)")
+                    help="with --full: skip the B=1 chunk latency and per-stage B=1 rooflines "
+                         "(batch sweeps)")
     ap.add_argument("--cpu-threads", type=int, default=0,
                     help="oracle threads (0: every CPU this process may use, see _cpu_share)")
     ap.add_argument("--scan-dt-proj", default="auto", choices=("auto", "on", "off"),
@@ -98,6 +106,13 @@ def _args():
                          "rehearse the multi-rank path with several ranks on one GPU)")
     ap.add_argument("--full-sequence", action="store_true",
                     help="stateless full-sequence forward (C2) instead of a stateful chunk")
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps also run the legs beside the headline: B=1 chunk "
+                         "p50 latency, scan / per-stage rooflines, CPU baseline (a plain run "
+                         "times the steps and prints the headline fields only)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the last timed step returned as DIR/<name>.npy (float32; "
+                         "large outputs as a fixed seeded sample of rows)")
     a = ap.parse_args()
     a.batch_default = a.batch is None
     if a.batch is None:
@@ -587,6 +602,62 @@ def _timed_steps(step, steps, warmup, world, device, sync):
     return max_over_ranks(elapsed, device), out
 
 
+DUMP_MAX_BYTES = 64 << 20  # --dump-outputs: all files together
+DUMP_SEED = 1234
+
+
+def _sample_rows(t, max_rows):
+    """t (..., C) as float32 rows on the CPU: every row when there are at most ``max_rows``,
+    else the rows at ``max_rows`` sorted positions drawn once from a CPU generator seeded
+    with DUMP_SEED — the same positions for the same shape in every run and every build."""
+    lead = tuple(t.shape[:-1])
+    rows = 1
+    for n in lead:
+        rows *= n
+    if rows <= max_rows:
+        return t.detach().float().reshape(rows, t.shape[-1]).cpu()
+    g = torch.Generator().manual_seed(DUMP_SEED)
+    flat = torch.sort(torch.randint(0, rows, (max_rows,), generator=g)).values
+    idx = []
+    for n in reversed(lead):
+        idx.append((flat % n).to(t.device))
+        flat = flat // n
+    return t.detach()[tuple(reversed(idx))].float().cpu()
+
+
+def dump_outputs(dirname, out, rank=0):
+    """--dump-outputs: what the timed path's last step returned, as float32 .npy files.
+    ``out`` is the forward's result: (x_vis, x_pool) for the full-sequence forward,
+    (x_vis, x_pool, next_state) for a stateful chunk (next_state: per layer
+    (conv_state, ssm_state)), or one tensor (the CPU stub).  x_pool is written whole, x_vis
+    as 8192 sampled (clip, token) rows, the states as 4096 sampled (clip, channel) rows per
+    layer stacked over the layers (_sample_rows).  Ranks above 0 prefix their files with
+    ``rank<r>_``."""
+    import numpy as np
+
+    arrays = {}
+    if torch.is_tensor(out):
+        arrays["out"] = _sample_rows(out, 8192)
+    else:
+        arrays["x_vis"] = _sample_rows(out[0], 8192)
+        if out[1] is not None:
+            arrays["x_pool"] = _sample_rows(out[1], 8192)
+        if len(out) > 2 and out[2] is not None:
+            st = out[2]
+            layers = [st[k] for k in sorted(st)] if isinstance(st, dict) else list(st)
+            pairs = [s if isinstance(s, (tuple, list)) else (None, s) for s in layers]
+            for name, col in (("state_conv", 0), ("state_ssm", 1)):
+                ts = [p[col] for p in pairs if p[col] is not None]
+                if ts:
+                    arrays[name] = torch.stack([_sample_rows(t, 4096) for t in ts])
+    total = sum(a.numel() * 4 for a in arrays.values())
+    assert total <= DUMP_MAX_BYTES, f"--dump-outputs would write {total} bytes"
+    os.makedirs(dirname, exist_ok=True)
+    prefix = f"rank{rank}_" if rank else ""
+    for name, a in arrays.items():
+        np.save(os.path.join(dirname, f"{prefix}{name}.npy"), a.numpy())
+
+
 def metric_name(cfg):
     """BASELINE.json's metric, named for the workload actually run (the headline string
     exactly for the C3 default, VideoMamba-M 16f)."""
@@ -646,15 +717,18 @@ def main_stub_cpu(args):
         per_rank, global_batch, strong = b - a, args.global_batch, True
     else:
         per_rank, global_batch, strong = args.batch, args.batch * world, False
-    w = torch.randn(64, 64)
-    x = torch.randn(max(per_rank, 1), 64)
+    g = torch.Generator().manual_seed(1000 + rank)
+    w = torch.randn(64, 64, generator=g)
+    x = torch.randn(max(per_rank, 1), 64, generator=g)
 
     def step():
         time.sleep(0.002 * (1 + rank))  # ranks differ: the max must be the slowest
         return x @ w
 
-    elapsed, _ = _timed_steps(step, args.steps, args.warmup, world, torch.device("cpu"),
-                              lambda: None)
+    elapsed, out = _timed_steps(step, args.steps, args.warmup, world, torch.device("cpu"),
+                                lambda: None)
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, out, rank)
     if rank == 0:
         line = _base_line(args, cfg, world, global_batch, per_rank, elapsed, strong)
         line["stub"] = "cpu"
@@ -716,7 +790,17 @@ def main():
     _progress(f"timed: {elapsed / args.steps * 1e3:.1f} ms per step")
     from videomamba_amd import kernels as K
     K.check_scan_sync()  # no one-launch scan hand-off timed out (outside the timed region)
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, out, rank)
+        _progress(f"outputs of the last timed step written to {args.dump_outputs}")
     line = _base_line(args, cfg, world, global_batch, B, elapsed, strong)
+    if not args.full:  # a plain run: the headline only
+        if rank == 0:
+            print(json.dumps(line), flush=True)
+        if world > 1:
+            dist.barrier()
+            dist.destroy_process_group()
+        return
 
     # streaming-chunk p50 latency at B=1 (one stateful chunk of the same clip shape):
     # replayed from a captured HIP graph (videomamba_amd/graphs.py), and eager for reference

@@ -6,5 +6,5 @@ cd "${GRAFT_REPO_ROOT:-$(dirname "$0")/../..}"
 export TMPDIR=/tmp MASTER_ADDR=127.0.0.1
 O=gpurun_out/${TAG:-r06aa}
 mkdir -p $O
-timeout -k 10 600 python -m torch.distributed.run --nnodes=1 --nproc-per-node 2 --master-addr 127.0.0.1 --master-port 29561 bench.py --gpus 2 --steps 3 --warmup 1 --batch 224 --no-b1 --no-cpu-baseline --scan-reps 2 --dist-backend gloo > $O/world2.json 2> $O/world2.err || { tail -30 $O/world2.err; exit 1; }
+timeout -k 10 600 python -m torch.distributed.run --nnodes=1 --nproc-per-node 2 --master-addr 127.0.0.1 --master-port 29561 bench.py --gpus 2 --steps 3 --warmup 1 --batch 224 --full --no-b1 --no-cpu-baseline --scan-reps 2 --dist-backend gloo > $O/world2.json 2> $O/world2.err || { tail -30 $O/world2.err; exit 1; }
 tail -c 1500 $O/world2.json

@@ -13,11 +13,11 @@ if [[ ${STEPS:-tests,bench,prof} == *tests* ]]; then
   tail -1 $O/smoke.log
 fi
 if [[ ${STEPS:-tests,bench,prof} == *bench* ]]; then
-  timeout -k 10 600 python -u bench.py > $O/bench.json 2> $O/bench.err || { echo bench failed; tail $O/bench.err; exit 1; }
+  timeout -k 10 600 python -u bench.py --full > $O/bench.json 2> $O/bench.err || { echo bench failed; tail $O/bench.err; exit 1; }
   cat $O/bench.json
 fi
 if [[ ${STEPS:-tests,bench,prof} == *prof* ]]; then
-  timeout -k 10 500 rocprofv3 --kernel-trace --stats --output-format csv -d $O/prof -o bench -- python bench.py --no-cpu-baseline > $O/prof_bench.log 2>&1 || { echo prof failed; tail $O/prof_bench.log; exit 1; }
+  timeout -k 10 500 rocprofv3 --kernel-trace --stats --output-format csv -d $O/prof -o bench -- python bench.py --full --no-cpu-baseline > $O/prof_bench.log 2>&1 || { echo prof failed; tail $O/prof_bench.log; exit 1; }
   echo prof done
 fi
 echo session done

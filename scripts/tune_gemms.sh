@@ -5,7 +5,7 @@ set -e
 cd "${GRAFT_REPO_ROOT:-$(dirname "$0")/..}"
 mkdir -p gpurun_out
 for B in ${BATCHES:-1 32 224}; do
-  VM_GEMM_TUNING=tune timeout -k 10 900 python bench.py --batch $B --steps 1 --warmup 1 \
+  VM_GEMM_TUNING=tune timeout -k 10 900 python bench.py --full --batch $B --steps 1 --warmup 1 \
     --p50-chunks 1 --scan-reps 1 --no-cpu-baseline > gpurun_out/tune_b$B.json
   echo "tuned B=$B"
 done

@@ -141,6 +141,56 @@ def test_bench_control_flow_world2_global_batch_split():
     assert abs(line["value"] - want) / want < 1e-3
 
 
+def test_bench_plain_run_is_the_headline_and_dump_outputs_repeats(tmp_path):
+    """A plain bench run (here the CPU stub, one process) prints the headline fields only —
+    the B=1 latency, roofline and CPU-baseline legs need --full — with --steps the number of
+    timed steps; --dump-outputs writes the last step's result as float32 .npy, identical
+    from run to run (seeded inputs)."""
+    import json
+    import subprocess
+    import sys
+
+    import numpy as np
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    got = []
+    for d in ("a", "b"):
+        out = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--stub-cpu",
+                              "--gpus", "1", "--steps", "3", "--warmup", "1", "--batch", "5",
+                              "--dump-outputs", str(tmp_path / d)],
+                             capture_output=True, text=True, timeout=120, cwd=root,
+                             env=dict(os.environ, OMP_NUM_THREADS="1"))
+        assert out.returncode == 0, out.stderr[-3000:]
+        line = json.loads(out.stdout.strip().splitlines()[-1])
+        assert line["steps"] == 3 and line["ms_per_step"] >= 2.0  # the stub sleeps 2 ms a step
+        for key in ("metric", "value", "unit", "higher_is_better", "dtype", "ms_per_step"):
+            assert key in line
+        for key in ("chunk_p50_ms", "roofline", "b1_kernels", "cpu_baseline"):
+            assert key not in line
+        assert sorted(os.listdir(tmp_path / d)) == ["out.npy"]
+        got.append(np.load(tmp_path / d / "out.npy"))
+    assert got[0].dtype == np.float32 and got[0].shape == (5, 64)
+    assert np.isfinite(got[0]).all() and np.array_equal(got[0], got[1])
+
+
+def test_bench_dump_sample_rows_is_fixed_and_reads_strided_outputs():
+    """bench._sample_rows (the --dump-outputs sample of a large output): the same sorted row
+    positions for the same shape on every call, taken through the leading dimensions of a
+    non-contiguous view (x_vis is feats[:, 1:]); a small output is written whole."""
+    import sys
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    sys.path.insert(0, root)
+    import bench
+    feats = torch.arange(7 * 12 * 3, dtype=torch.float32).view(7, 12, 3).to(torch.bfloat16)
+    x_vis = feats[:, 1:]
+    whole = bench._sample_rows(x_vis, 1000)
+    assert whole.dtype == torch.float32 and torch.equal(whole, x_vis.float().reshape(77, 3))
+    a, b = bench._sample_rows(x_vis, 20), bench._sample_rows(x_vis, 20)
+    assert a.shape == (20, 3) and torch.equal(a, b)
+    g = torch.Generator().manual_seed(bench.DUMP_SEED)
+    rows = torch.sort(torch.randint(0, 77, (20,), generator=g)).values
+    assert torch.equal(a, whole[rows])
+
+
 def _encoder_shard_worker(rank, world, port, q, split=False):
     """One rank of the batch-sharded encoder: its contiguous clip range through the HIP
     encoder on cuda:0, then the pooled-feature all-gather (gloo, so CPU tensors).  ``split``:

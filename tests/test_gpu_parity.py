@@ -87,9 +87,11 @@ def _oracle_scan(Bz, D, L, N):
                                       (2, 24, 777, 8), (3, 20, 100, 4), (1, 8, 0, 16),
                                       (1, 16, 9000, 16)])   # > 8 waves x 512 steps
 def test_scan_matches_oracle_random(Bz, D, L, N):
-    """Channel-major operands: the time-parallel kernel (its state-split and pipelined
-    small-grid forms are picked by grid size: (1, 40, 3137) runs split, (64, 72, 300) the
-    one-wave form)."""
+    """Channel-major fp32 operands: the time-parallel kernel's plain form only — the
+    state-split and pipelined small-grid forms are bf16-only (launch_v5_auto / launch_v5,
+    vm_scan.hip) and are compared with a reference in test_gpu_scan_matrix.py.  The shapes
+    differ in the steps per lane K that ``cost(out_len)`` picks: K = 10 for L = 3137, 9000
+    and the empty L = 0, K = 8 for L = 300, 777 and 100."""
     u, delta, A, Bm, Cm, Dv, z, bias, init = _rand_scan(Bz, D, L, N, torch.float32, 11 + L)
     ref_y, ref_h = _oracle_scan(Bz, D, L, N)
     cu = lambda t: None if t is None else t.to(DEV)  # noqa: E731

@@ -998,7 +998,9 @@ __global__ __launch_bounds__(64 * kChW) void scan_chunk_kernel(const ScanParams 
 #pragma unroll
     for (int i = 0; i < kChSPW; ++i) sH[j][n + i][c] = v.v[i];
   };
-  const int voff = lane * ES;
+  // lanes past dim load the group's last live channel (as scan_seq_kernel): lane * ES would
+  // read past the row, and on the last step of the last batch row past the operand's end
+  const int voff = (d - d0) * ES;
   const int voff_st = active ? voff : kSeqDead;
   const auto ur = uniform_rsrc(static_cast<const T*>(p.u) + b * p.u_sb + d0);
   const auto dr_ = uniform_rsrc(static_cast<const T*>(p.delta) + b * p.dl_sb + d0);
@@ -1051,7 +1053,8 @@ __global__ __launch_bounds__(64 * kChW) void scan_chunk_kernel(const ScanParams 
     const int bt1 = min(L, bt0 + kChW * w.T);
     if (bt1 > bt0) {
       const char* base = reinterpret_cast<const char*>(Bq) + static_cast<long long>(bt0) * bsl;
-      const int span = (bt1 - bt0 - 1) * static_cast<int>(bsl) + 2 * kMaxN * ES;
+      // (a B row holds C too only under BC1: separate B rows end kMaxN elements in)
+      const int span = (bt1 - bt0 - 1) * static_cast<int>(bsl) + (BC1 ? 2 : 1) * kMaxN * ES;
       const int line = static_cast<int>(threadIdx.x) * 128;
       // (the loads' values are consumed only after the start-up wait below: a consumer here
       // made hipcc wait for each warm-up load on the spot)

@@ -219,7 +219,7 @@ VARIANTS = {
     "dtp_yearly": [("vm_scan_seq.hip", "constexpr bool kDtpYLate = true;", "constexpr bool kDtpYLate = false;")],
     # chunked scan: 16-wave workgroups (one state per wave in the composition / hand-off,
     # 4 waves per SIMD) instead of 8
-    "ch16": [("vm_scan_seq.hip", "constexpr int kChW = 8;  // segments (waves) per workgroup",
+    "ch16": [("vm_scan_plan.h", "constexpr int kChW = 8;  // segments (waves) per workgroup",
               "constexpr int kChW = 16;  // segments (waves) per workgroup")],
     # persistent GEMM: tight wait before the output stores, the next tile's first two waits
     # skipped (kTileStoreWait 1) instead of draining the stores at the next wait

@@ -1,6 +1,6 @@
 """Chunked token-major scan time vs forced segment count (M-16f mixer geometry, bf16,
 stateful, delta softplus, z gate), HIP events over back-to-back launches.  Used to fit the
-segment cost model in vm_scan_seq.hip::choose_segments.
+segment cost model in vm_scan_plan.h::choose_segments.
     python scripts/diag/scan_segments_sweep.py  (env CASES="B:L,..." SEGS="0 50 100 ...")
 DTP=1: the dt_proj-inside form (vm_selective_scan_dtproj_fwd, segments of <= 64 steps)."""
 import json

@@ -3,8 +3,11 @@ CPU tests (tests/test_public_api_contract.py, tests/test_videomamba_regressions.
 the C-ABI library load + export check.  No kernel compute happens here (no GPU)."""
 
 import ctypes
+import json
 import os
 import re
+import shutil
+import subprocess
 from types import SimpleNamespace
 from typing import Any
 
@@ -297,7 +300,7 @@ def test_scan_workspace_query_without_gpu():
 
 
 def test_scan_segment_cost_model_choices_without_gpu():
-    """The measured segment cost model (vm_scan_seq.hip::choose_segments, fitted to
+    """The measured segment cost model (vm_scan_plan.h::choose_segments, fitted to
     profiles/r02_scan_segments_sweep.jsonl) as seen through the sync-buffer query:
     nblk blocks of {tag, value} granules per (row, 64-channel group) at M-16f (D = 1152, 18
     groups).  B = 1:
@@ -309,6 +312,73 @@ def test_scan_segment_cost_model_choices_without_gpu():
     assert nblk(1, 3137) == 14 and nblk(1, 12545) == 14
     assert nblk(2, 3137) == nblk(4, 3137) == nblk(8, 3137) == 7
     assert lib.vm_selective_scan_sync_bytes(72, 1152, 3137, 16, 0) == 0
+
+
+def _scan_size_query_rows():
+    table = json.load(open(os.path.join(ROOT, "tests", "golden", "scan_size_queries.json")))
+    assert table["columns"] == ["batch", "dim", "seqlen", "segments", "dstate", "workspace_bytes",
+                                "sync_bytes", "chunk_steps"]
+    return table["rows"]
+
+
+def test_scan_size_queries_reproduce_the_recorded_table():
+    """The three size queries against tests/golden/scan_size_queries.json: their values as
+    recorded from the library built at the commit the file names (before the host side was
+    folded into vm_scan_plan.h::plan_scan), without a device, so with the 256-CU
+    calibration.  Every row must come back unchanged."""
+    lib = _lib.load()
+    rows = _scan_size_query_rows()
+    assert len(rows) >= 300
+    bad = []
+    for b, d, l, seg, n, ws, sync, steps in rows:
+        got = (lib.vm_selective_scan_workspace_bytes(b, d, l, n, seg),
+               lib.vm_selective_scan_sync_bytes(b, d, l, n, seg),
+               lib.vm_selective_scan_chunk_steps(b, d, l, n, seg))
+        if got != (ws, sync, steps):
+            bad.append(((b, d, l, seg, n), (ws, sync, steps), got))
+    assert not bad, bad[:5]
+
+
+def test_scan_dtproj_segmented_pays_counts_the_library_s_workgroups(monkeypatch):
+    """kernels.scan_dtproj_segmented_pays derives the chunked scan's workgroup count in
+    Python (segments of `steps`, blocks of 8: a copy of kChW).  For every segmented row of
+    the recorded table that count must equal the library's own, read off the sync-buffer
+    size (one 17 x 64 granule block of 8 bytes per workgroup after the 16-byte header): with
+    exactly that many CUs a segment of at most 64 steps pays, with one fewer it does not."""
+    from videomamba_amd import kernels as K
+    cus = {}
+    monkeypatch.setattr(K, "_cu_count", lambda device: cus["n"])
+    seen = 0
+    for b, d, l, seg, n, ws, sync, steps in _scan_size_query_rows():
+        if steps <= 0:
+            continue
+        wgs, rem = divmod(sync - 16, 17 * 64 * 8)
+        assert rem == 0 and wgs >= 1
+        cus["n"] = wgs
+        assert K.scan_dtproj_segmented_pays(b, d, l, n, "cpu", seg) == (steps <= 64), (b, d, l, seg)
+        cus["n"] = wgs - 1
+        assert not K.scan_dtproj_segmented_pays(b, d, l, n, "cpu", seg), (b, d, l, seg)
+        seen += steps <= 64
+    assert seen >= 100
+
+
+def test_scan_plan_check_program_passes_under_sanitizers(tmp_path):
+    """tests/host/scan_plan_check.cpp walks vm_scan_plan.h::plan_scan over shapes x CU
+    counts x operand facts x buffer offers and exits non-zero on any inconsistent plan
+    (overlapping workspace regions, uncovered steps, a one-launch grid that is not resident,
+    ...).  Built as a program of its own with the host compiler under ASan + UBSan, the
+    sanitizer runtimes linked into the program (clang's default; g++ needs the flags)."""
+    rocm_clang = "/opt/rocm/llvm/bin/clang++"
+    cxx = [rocm_clang] if os.path.exists(rocm_clang) else \
+        [shutil.which("g++") or "g++", "-static-libasan", "-static-libubsan"]
+    exe = str(tmp_path / "scan_plan_check")
+    subprocess.run(cxx + ["-std=c++17", "-O1", "-g", "-fsanitize=address,undefined",
+                    "-fno-sanitize-recover=all", "-I", os.path.join(ROOT, "videomamba_amd", "csrc"),
+                    os.path.join(ROOT, "tests", "host", "scan_plan_check.cpp"), "-o", exe],
+                   check=True, timeout=120)
+    run = subprocess.run([exe], capture_output=True, text=True, timeout=120)
+    assert run.returncode == 0, run.stdout + run.stderr
+    assert " 0 failures" in run.stdout
 
 
 def test_library_reads_no_environment():

@@ -280,7 +280,7 @@ def _run_tm_form(form, row, dt, L, steps=None):
 def test_token_major_form_matches_ref64(form, dt, row):
     """(2, 136, 150, N): D = 136 is two full 64-channel waves and one with 8 live lanes —
     and in scan_seq_kernel a wholly dead fourth wave (the d0 clamp, kSeqDead stores).
-    Dispatch relied on (vm_scan_seq.hip, seq_launch / launch_seq_mode / launch_chunk):
+    Dispatch relied on (vm_scan_plan.h::plan_scan, then vm_scan_seq.hip seq_launch -> launch_seq / launch_chunk):
     * single: ``scan_segments=1`` -> scan_seq_kernel MODE 0; scalar-load B/C when
       seq_sgpr_bc holds (N = 16, unit state stride, 4-byte aligned rows: the ``_tm`` views
       and the mixer layout), BC1 when C directly follows B in one row (mixer layout only),
@@ -348,8 +348,8 @@ def test_paired_form_matches_ref64(form, dt, frame, row):
     rows >= split scan with their own A / D / bias / h0 (a row without D / bias / h0 drops
     it for both directions) and store step t at row t + (L - F) - 2F floor(t / F) (L - 1 - t
     for F = 1).  ``p.split < p.batch`` selects the PAIR instantiations: of scan_seq_kernel
-    with ``scan_segments=1`` (launch_seq_mode), of scan_chunk_kernel with
-    ``scan_segments=20`` (launch_chunk_t), two launches or one as above (grid 3 x 3 x 4)."""
+    with ``scan_segments=1`` (launch_seq), of scan_chunk_kernel with
+    ``scan_segments=20`` (launch_chunk), two launches or one as above (grid 3 x 3 x 4)."""
     _run_pair_form(form, row, dt, 150, frame)
 
 

@@ -3,10 +3,9 @@
 #pragma once
 
 #include "vm_common.h"
+#include "vm_scan_plan.h"
 
 namespace vm {
-
-constexpr int kMaxN = 16;
 
 // Every (batch, channel|state, step) operand carries three element strides; the
 // channel-major kernels require the step stride to be 1, the token-major ones require the
@@ -50,25 +49,29 @@ __device__ __forceinline__ PairSel pair_sel(const ScanParams& p, int b) {
 }
 
 
-// Token-major path (vm_scan_seq.hip).  Workspace for the time-segmented form, in bytes;
-// 0 when the single-pass form is chosen.  `segments` receives the chosen segment count.
-// segments: 0 = cost model, > 0 forced.  cus: the CU count the cost model sizes for
-// (0 = the current device's; kCalibCUs = 256 when no device can be queried).
-size_t seq_workspace_bytes(int batch, int dim, int seqlen, int segments, int* chosen,
-                           int cus = 0);
-// Launch; `workspace` must hold seq_workspace_bytes() (or be larger).  Returns false when
-// the operands do not fit the token-major kernels (the caller reports the error).
+// Token-major path (vm_scan_seq.hip).  Every decision about its form, geometry and buffer
+// layout is a ScanPlan (vm_scan_plan.h).
+// The ABI size queries, for the current device's CU count (kCalibCUs when none can be
+// queried); segments: 0 = cost model, > 0 forced.  Workspace bytes of the time-segmented
+// form (0: single pass); bytes of the zeroed sync buffer the one-launch chunked form needs
+// (word 0 is the sticky error word, non-zero after a launch whose block handoff timed out
+// (vm_selective_scan_sync_status), word 1 the epoch, word 2 the launch's start count, word 3
+// pad, then the {tag, value} hand-off granules); steps per segment of the chunked form (0:
+// single pass), for the host's choice of dt_proj placement.
+size_t seq_workspace_bytes(int batch, int dim, int seqlen, int segments);
+size_t seq_sync_bytes(int batch, int dim, int seqlen, int segments);
+int seq_chunk_steps(int batch, int dim, int seqlen, int segments);
+// False when the operands do not fit the token-major kernels (the caller reports the error).
 bool seq_supported(const ScanParams& p, int dtype);
-void seq_launch(const ScanParams& p, int dtype, int segments, void* workspace,
-                size_t workspace_bytes, void* sync, size_t sync_bytes, hipStream_t s);
-// Bytes of the zeroed sync buffer the one-launch chunked form needs (0: single pass).
-// Word 0 is the sticky error word (non-zero after a launch whose block handoff timed out;
-// vm_selective_scan_sync_status), word 1 the epoch, word 2 the launch's start count, word 3
-// pad, then the {tag, value} hand-off granules.
-constexpr int kSyncHeaderWords = 4;
-size_t seq_sync_bytes(int batch, int dim, int seqlen, int segments, int cus = 0);
+// The plan of one launch, from the operands and the stream's device: an entry computes it
+// once and hands it to its checks and its launch.  `pair` / `dtp`: a paired scan / dt_proj
+// inside the scan; pass 0 bytes for a null workspace or sync buffer.
+ScanPlan seq_plan(const ScanParams& p, int dtype, int segments, bool pair, bool dtp,
+                  size_t workspace_bytes, size_t sync_bytes, hipStream_t s);
+void seq_launch(const ScanParams& p, int dtype, const ScanPlan& pl, void* workspace, void* sync,
+                hipStream_t s);
 // Paired scans need the scalar-B/C kernels and, when segmented, the chunked form.
-bool seq_pair_supported(const ScanParams& p, int dtype, int segments, size_t workspace_bytes);
+bool seq_pair_supported(const ScanParams& p, int dtype, const ScanPlan& pl);
 
 // dt_proj folded into the single-pass token-major scan (vm_selective_scan_dtproj_fwd):
 // delta = bf16(dt_low @ W_dt^T) computed per 16-step block on the matrix cores.
@@ -82,10 +85,9 @@ struct DtpArgs {
 };
 bool seq_dtp_supported(const ScanParams& p, const DtpArgs& q, int dtype, int dt_rank);
 void seq_dtp_launch(const ScanParams& p, const DtpArgs& q, int dt_rank, hipStream_t s);
-int seq_chunk_steps(int batch, int dim, int seqlen, int segments);
-bool seq_dtp_chunk_supported(const ScanParams& p, const DtpArgs& q, int dtype, int segments,
-                             size_t workspace_bytes);
-void seq_dtp_chunk_launch(const ScanParams& p, const DtpArgs& q, int segments, void* workspace,
-                          size_t workspace_bytes, void* sync, size_t sync_bytes, hipStream_t s);
+bool seq_dtp_chunk_supported(const ScanParams& p, const DtpArgs& q, int dtype,
+                             const ScanPlan& pl);
+void seq_dtp_chunk_launch(const ScanParams& p, const DtpArgs& q, const ScanPlan& pl,
+                          void* workspace, void* sync, hipStream_t s);
 
 }  // namespace vm

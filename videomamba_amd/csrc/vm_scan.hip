@@ -467,21 +467,42 @@ struct PairArgs {
 };
 }  // namespace
 
-static int scan_entry(
-    const char* name,
-    const void* u, long long u_sb, long long u_sd, long long u_sl,
-    const void* delta, long long dl_sb, long long dl_sd, long long dl_sl,
-    const float* A,
-    const void* B, long long b_sb, long long b_sn, long long b_sl,
-    const void* C, long long c_sb, long long c_sn, long long c_sl,
-    const float* D, const void* z, long long z_sb, long long z_sd, long long z_sl,
-    const float* delta_bias, int delta_softplus,
-    const void* h0, int h0_dtype, long long h0_sb, long long h0_sd,
-    void* h_last, int hl_dtype, long long hl_sb, long long hl_sd,
-    void* out, long long o_sb, long long o_sd, long long o_sl, int out_len,
-    int batch, int dim, int seqlen, int dstate, int dtype, const PairArgs* pair,
-    int segments, void* workspace, long long workspace_bytes, void* sync, long long sync_bytes,
-    vm_stream_t stream) {
+#define VM_SCAN_ARGS                                                                  \
+  const void *u, long long u_sb, long long u_sd, long long u_sl, const void *delta,   \
+      long long dl_sb, long long dl_sd, long long dl_sl, const float *A, const void *B, \
+      long long b_sb, long long b_sn, long long b_sl, const void *C, long long c_sb,     \
+      long long c_sn, long long c_sl, const float *D, const void *z, long long z_sb,     \
+      long long z_sd, long long z_sl, const float *delta_bias, int delta_softplus,       \
+      const void *h0, int h0_dtype, long long h0_sb, long long h0_sd, void *h_last,      \
+      int hl_dtype, long long hl_sb, long long hl_sd, void *out, long long o_sb,         \
+      long long o_sd, long long o_sl, int out_len, int batch, int dim, int seqlen,       \
+      int dstate, int dtype
+#define VM_SCAN_PASS                                                                  \
+  u, u_sb, u_sd, u_sl, delta, dl_sb, dl_sd, dl_sl, A, B, b_sb, b_sn, b_sl, C, c_sb, c_sn, \
+      c_sl, D, z, z_sb, z_sd, z_sl, delta_bias, delta_softplus, h0, h0_dtype, h0_sb,      \
+      h0_sd, h_last, hl_dtype, hl_sb, hl_sd, out, o_sb, o_sd, o_sl, out_len, batch, dim,  \
+      seqlen, dstate, dtype
+
+// The operands of a plain scan (split == batch), for every scan entry.
+static ScanParams scan_params(VM_SCAN_ARGS) {
+  (void)dtype;
+  ScanParams p{};
+  p.u = u; p.delta = delta; p.A = A; p.B = B; p.C = C; p.D = D; p.z = z; p.dbias = delta_bias;
+  p.h0 = h0; p.hl = h_last; p.out = out;
+  p.u_sb = u_sb; p.u_sd = u_sd; p.dl_sb = dl_sb; p.dl_sd = dl_sd;
+  p.b_sb = b_sb; p.b_sn = b_sn; p.c_sb = c_sb; p.c_sn = c_sn;
+  p.z_sb = z_sb; p.z_sd = z_sd; p.o_sb = o_sb; p.o_sd = o_sd;
+  p.u_sl = u_sl; p.dl_sl = dl_sl; p.b_sl = b_sl; p.c_sl = c_sl; p.z_sl = z_sl; p.o_sl = o_sl;
+  p.h0_sb = h0_sb; p.h0_sd = h0_sd; p.hl_sb = hl_sb; p.hl_sd = hl_sd;
+  p.batch = batch; p.dim = dim; p.seqlen = seqlen; p.out_len = out_len; p.dstate = dstate;
+  p.softplus = delta_softplus; p.h0_dtype = h0_dtype; p.hl_dtype = hl_dtype;
+  p.split = batch;
+  return p;
+}
+
+static int scan_entry(const char* name, VM_SCAN_ARGS, const PairArgs* pair, int segments,
+                      void* workspace, long long workspace_bytes, void* sync,
+                      long long sync_bytes, vm_stream_t stream) {
   if (!u || !delta || !A || !B || !C || !out) {
     vmhost::set_error("%s: null required pointer", name);
     return VM_E_INVALID;
@@ -497,19 +518,15 @@ static int scan_entry(
     return VM_E_INVALID;
   }
   if (batch == 0 || dim == 0) return VM_OK;
-  ScanParams p{};
-  p.u = u; p.delta = delta; p.A = A; p.B = B; p.C = C; p.D = D; p.z = z; p.dbias = delta_bias;
-  p.h0 = h0; p.hl = h_last; p.out = out;
-  p.u_sb = u_sb; p.u_sd = u_sd; p.dl_sb = dl_sb; p.dl_sd = dl_sd;
-  p.b_sb = b_sb; p.b_sn = b_sn; p.c_sb = c_sb; p.c_sn = c_sn;
-  p.z_sb = z_sb; p.z_sd = z_sd; p.o_sb = o_sb; p.o_sd = o_sd;
-  p.u_sl = u_sl; p.dl_sl = dl_sl; p.b_sl = b_sl; p.c_sl = c_sl; p.z_sl = z_sl; p.o_sl = o_sl;
-  p.h0_sb = h0_sb; p.h0_sd = h0_sd; p.hl_sb = hl_sb; p.hl_sd = hl_sd;
-  p.batch = batch; p.dim = dim; p.seqlen = seqlen; p.out_len = out_len; p.dstate = dstate;
-  p.softplus = delta_softplus; p.h0_dtype = h0_dtype; p.hl_dtype = hl_dtype;
-  p.split = batch;
+  ScanParams p = scan_params(VM_SCAN_PASS);
   hipStream_t s = static_cast<hipStream_t>(stream);
-  const size_t ws_bytes = workspace_bytes > 0 ? static_cast<size_t>(workspace_bytes) : 0;
+  // token-major operands: one plan, from the stream's device, for the checks and the launch
+  const bool token_major = seq_supported(p, dtype);
+  const ScanPlan pl =
+      token_major ? seq_plan(p, dtype, segments, pair != nullptr, false,
+                             workspace && workspace_bytes > 0 ? static_cast<size_t>(workspace_bytes) : 0,
+                             sync && sync_bytes > 0 ? static_cast<size_t>(sync_bytes) : 0, s)
+                  : ScanPlan{};
   if (pair) {
     const int F = pair->frame_len;
     if (!pair->A || pair->split * 2 != batch || F < 1 || seqlen % F ||
@@ -517,7 +534,7 @@ static int scan_entry(
       vmhost::set_error("%s: need batch == 2*split, A_bwd, and frame_len dividing seqlen", name);
       return VM_E_INVALID;
     }
-    if (!seq_supported(p, dtype) || !seq_pair_supported(p, dtype, segments, workspace ? ws_bytes : 0)) {
+    if (!token_major || !seq_pair_supported(p, dtype, pl)) {
       vmhost::set_error("%s: paired scans take token-major operands with 16 unit-stride states "
                         "and, when segmented, the vm_selective_scan_workspace_bytes workspace",
                         name);
@@ -535,9 +552,8 @@ static int scan_entry(
     }
   }
   // Token-major operands (channel stride 1): channel-per-lane sequential kernels.
-  if (seq_supported(p, dtype)) {
-    seq_launch(p, dtype, segments, workspace, ws_bytes, sync,
-               sync_bytes > 0 ? static_cast<size_t>(sync_bytes) : 0, s);
+  if (token_major) {
+    seq_launch(p, dtype, pl, workspace, sync, s);
     return vmhost::launch_status(name);
   }
   // Channel-major operands (step stride 1): time-parallel kernels.
@@ -559,22 +575,6 @@ static int scan_entry(
   return vmhost::launch_status(name);
 }
 
-#define VM_SCAN_ARGS                                                                  \
-  const void *u, long long u_sb, long long u_sd, long long u_sl, const void *delta,   \
-      long long dl_sb, long long dl_sd, long long dl_sl, const float *A, const void *B, \
-      long long b_sb, long long b_sn, long long b_sl, const void *C, long long c_sb,     \
-      long long c_sn, long long c_sl, const float *D, const void *z, long long z_sb,     \
-      long long z_sd, long long z_sl, const float *delta_bias, int delta_softplus,       \
-      const void *h0, int h0_dtype, long long h0_sb, long long h0_sd, void *h_last,      \
-      int hl_dtype, long long hl_sb, long long hl_sd, void *out, long long o_sb,         \
-      long long o_sd, long long o_sl, int out_len, int batch, int dim, int seqlen,       \
-      int dstate, int dtype
-#define VM_SCAN_PASS                                                                  \
-  u, u_sb, u_sd, u_sl, delta, dl_sb, dl_sd, dl_sl, A, B, b_sb, b_sn, b_sl, C, c_sb, c_sn, \
-      c_sl, D, z, z_sb, z_sd, z_sl, delta_bias, delta_softplus, h0, h0_dtype, h0_sb,      \
-      h0_sd, h_last, hl_dtype, hl_sb, hl_sd, out, o_sb, o_sd, o_sl, out_len, batch, dim,  \
-      seqlen, dstate, dtype
-
 extern "C" int vm_selective_scan_fwd(VM_SCAN_ARGS, int segments, void* workspace,
                                      long long workspace_bytes, void* sync,
                                      long long sync_bytes, vm_stream_t stream) {
@@ -592,8 +592,6 @@ extern "C" int vm_selective_scan_bidir_fwd(VM_SCAN_ARGS, int split, const float*
   return scan_entry("vm_selective_scan_bidir_fwd", VM_SCAN_PASS, &pair, segments, workspace,
                     workspace_bytes, sync, sync_bytes, stream);
 }
-#undef VM_SCAN_ARGS
-#undef VM_SCAN_PASS
 
 extern "C" int vm_selective_scan_dtproj_fwd(
     const void* u, long long u_sb, long long u_sd, long long u_sl, const void* dt_low,
@@ -617,17 +615,10 @@ extern "C" int vm_selective_scan_dtproj_fwd(
     return VM_E_INVALID;
   }
   if (batch == 0 || dim == 0) return VM_OK;
-  ScanParams p{};
-  p.u = u; p.delta = nullptr; p.A = A; p.B = B; p.C = C; p.D = D; p.z = z; p.dbias = delta_bias;
-  p.h0 = h0; p.hl = h_last; p.out = out;
-  p.u_sb = u_sb; p.u_sd = u_sd; p.dl_sb = 0; p.dl_sd = 1;
-  p.b_sb = b_sb; p.b_sn = b_sn; p.c_sb = c_sb; p.c_sn = c_sn;
-  p.z_sb = z_sb; p.z_sd = z_sd; p.o_sb = o_sb; p.o_sd = o_sd;
-  p.u_sl = u_sl; p.dl_sl = 0; p.b_sl = b_sl; p.c_sl = c_sl; p.z_sl = z_sl; p.o_sl = o_sl;
-  p.h0_sb = h0_sb; p.h0_sd = h0_sd; p.hl_sb = hl_sb; p.hl_sd = hl_sd;
-  p.batch = batch; p.dim = dim; p.seqlen = seqlen; p.out_len = out_len; p.dstate = dstate;
-  p.softplus = delta_softplus; p.h0_dtype = h0_dtype; p.hl_dtype = hl_dtype;
-  p.split = batch;
+  // no delta stream: the scan computes dt from the x_dbl rows
+  const void* delta = nullptr;
+  const long long dl_sb = 0, dl_sd = 1, dl_sl = 0;
+  const ScanParams p = scan_params(VM_SCAN_PASS);
   DtpArgs q{};
   q.dtl = static_cast<const bf16_t*>(dt_low); q.dtl_sb = dtl_sb; q.dtl_sl = dtl_sl;
   q.wdt = static_cast<const bf16_t*>(w_dt); q.wdt_ld = w_dt_ld; q.dt_rank = dt_rank;
@@ -637,9 +628,12 @@ extern "C" int vm_selective_scan_dtproj_fwd(
   }
   // the segmented form when the cost model (or `segments`) asks for one: dt_proj inside the
   // chunked scan, in conv_proj's arithmetic (ABI v11)
-  if (seq_chunk_steps(batch, dim, seqlen, segments) > 0) {
-    if (!seq_dtp_chunk_supported(p, q, dtype, segments, static_cast<size_t>(workspace_bytes)) ||
-        !workspace) {
+  const ScanPlan pl = seq_plan(p, dtype, segments, false, true,
+                               workspace ? static_cast<size_t>(workspace_bytes) : 0,
+                               sync ? static_cast<size_t>(sync_bytes) : 0,
+                               static_cast<hipStream_t>(stream));
+  if (pl.chosen > 1) {
+    if (!seq_dtp_chunk_supported(p, q, dtype, pl)) {
       vmhost::set_error("%s: the segmented form needs bf16 token-major operands with z, "
                         "softplus, 16 states, C directly after B in the x_dbl rows, segments of "
                         "at most 64 steps (vm_selective_scan_chunk_steps), a (dim, 32 | 64) W_dt "
@@ -647,8 +641,7 @@ extern "C" int vm_selective_scan_dtproj_fwd(
                         "vm_selective_scan_workspace_bytes", name);
       return VM_E_INVALID;
     }
-    seq_dtp_chunk_launch(p, q, segments, workspace, static_cast<size_t>(workspace_bytes), sync,
-                         static_cast<size_t>(sync_bytes), static_cast<hipStream_t>(stream));
+    seq_dtp_chunk_launch(p, q, pl, workspace, sync, static_cast<hipStream_t>(stream));
     return vmhost::launch_status(name);
   }
   if (!seq_dtp_supported(p, q, dtype, dt_rank)) {
@@ -661,6 +654,9 @@ extern "C" int vm_selective_scan_dtproj_fwd(
   return vmhost::launch_status(name);
 }
 
+#undef VM_SCAN_ARGS
+#undef VM_SCAN_PASS
+
 extern "C" int vm_selective_scan_chunk_steps(int batch, int dim, int seqlen, int dstate,
                                              int segments) {
   if (batch <= 0 || dim <= 0 || seqlen < 0 || dstate < 1 || dstate > kMaxN || segments < 0)
@@ -671,7 +667,7 @@ extern "C" int vm_selective_scan_chunk_steps(int batch, int dim, int seqlen, int
 extern "C" long long vm_selective_scan_workspace_bytes(int batch, int dim, int seqlen,
                                                        int dstate, int segments) {
   if (batch <= 0 || dim <= 0 || seqlen < 0 || dstate < 1 || dstate > kMaxN) return 0;
-  return static_cast<long long>(seq_workspace_bytes(batch, dim, seqlen, segments, nullptr));
+  return static_cast<long long>(seq_workspace_bytes(batch, dim, seqlen, segments));
 }
 
 extern "C" long long vm_selective_scan_sync_bytes(int batch, int dim, int seqlen, int dstate,

@@ -23,8 +23,12 @@
 //                              (PASS 3 below);
 //   scan_seq_kernel MODE 1 / 2 + scan_seq_carry_kernel: the summary / carry / final form for
 //                              operands the scalar-load path cannot take (LDS-staged B / C).
+// Host side (end of the file): which of these runs, with what geometry and workspace layout,
+// is one ScanPlan (vm_scan_plan.h::plan_scan); the launchers only read it.
 
 #include <stdlib.h>
+
+#include <type_traits>
 
 #include "vm_scan.h"
 
@@ -41,7 +45,6 @@ typedef float f2 __attribute__((ext_vector_type(2)));
 
 constexpr int kTS = 32;       // steps per LDS block
 constexpr int kPF = 8;        // u / delta / z prefetch distance in steps
-constexpr int kMaxSeg = 256;  // segments per sequence
 constexpr int kSeqNW = 2;     // waves (channel groups of 64) per workgroup
 constexpr bool kSeqXcdRemap = true;  // grids renumbered per XCD (see scan_seq_kernel)
 constexpr bool kSeqDeltaAhead = true;  // next step's delta computed a step early
@@ -96,16 +99,18 @@ __device__ __forceinline__ float raw_f32(uint32_t r) {
 // MODE 0: single pass (entry state h0), MODE 1: summary, MODE 2: final with entry states.
 // SB: B_t / C_t (16 states, unit state stride, 4-byte aligned rows) come in as scalar
 // loads — wave-uniform SGPR operands of the VALU ops, one step ahead — instead of the LDS
-// staging + broadcast reads.
-// PK (requires SB): the four per-state VALU ops run as packed-f32 ops over state pairs
+// staging + broadcast reads.  Single pass only: seq_launch sends every segmented scan with
+// such operands to scan_chunk_kernel, so MODE 1 / 2 exist with LDS staging alone.
+// PK (always with SB): the four per-state VALU ops run as packed-f32 ops over state pairs
 // (v_pk_mul_f32 delta*A and (delta*u)*B, v_pk_fma_f32 for h and y) — B/C pairs are SGPR
 // pairs — leaving the 16 v_exp_f32 unpaired.  Measured in the step mix
 // (tools/probes/pk_rate.hip) a pair costs ~4.7 cycles per packed op against ~3.6 per
 // scalar op in dependent chains, so the step drops from ~343 to ~265 cycles per wave.
-template <typename T, int NW, int MODE, bool SP, bool HZ, bool SB, bool PK, bool BC1 = false,
-          bool PAIR = false>
-__global__ __launch_bounds__(64 * NW) void scan_seq_kernel(const ScanParams p, const SeqWork w) {
-  static_assert(!PK || SB, "packed pairs take B/C from SGPR pairs");
+template <typename T, int MODE, bool SP, bool HZ, bool SB, bool BC1 = false, bool PAIR = false>
+__global__ __launch_bounds__(64 * kSeqNW) void scan_seq_kernel(const ScanParams p, const SeqWork w) {
+  constexpr int NW = kSeqNW;
+  constexpr bool PK = SB;  // packed pairs take B/C from SGPR pairs
+  static_assert(MODE == 0 || !SB, "the summary / final passes stage B / C in LDS");
   static_assert(NW * 64 >= 4 * kTS, "B/C staging needs 4 threads per block step");
   typedef __attribute__((address_space(4))) const uint32_t* cptr;
   constexpr int NWD = kMaxN * sizeof(T) / 4;  // 32-bit words per B (or C) row
@@ -231,7 +236,7 @@ __global__ __launch_bounds__(64 * NW) void scan_seq_kernel(const ScanParams p, c
 #pragma unroll
       for (int i = 0; i < NWD; ++i) {
         dst[i] = bp[i];
-        if constexpr (MODE != 1) dst[NWD + i] = cp[i];
+        dst[NWD + i] = cp[i];
       }
     }
   };
@@ -344,18 +349,12 @@ __global__ __launch_bounds__(64 * NW) void scan_seq_kernel(const ScanParams p, c
           const f2 x = dl2 * A2[q];
           const f2 a = {__builtin_amdgcn_exp2f(x.x), __builtin_amdgcn_exp2f(x.y)};
           h[q] = __builtin_elementwise_fma(a, h[q], du2 * Bp);
-          if constexpr (MODE != 1) {
-            if (q & 1) yb = __builtin_elementwise_fma(h[q], Cp, yb);
-            else ya = __builtin_elementwise_fma(h[q], Cp, ya);
-          }
+          if (q & 1) yb = __builtin_elementwise_fma(h[q], Cp, yb);
+          else ya = __builtin_elementwise_fma(h[q], Cp, ya);
         }
-        if constexpr (MODE == 1) {
-          sdel += dl;
-        } else {
-          const f2 ys = ya + yb;
-          const float y = gate(ys.x + ys.y);
-          bstore<T>(from_f32<T>(y), orr, live ? voff_st : kSeqDead, ps.orow(t) * os);
-        }
+        const f2 ys = ya + yb;
+        const float y = gate(ys.x + ys.y);
+        bstore<T>(from_f32<T>(y), orr, live ? voff_st : kSeqDead, ps.orow(t) * os);
         return;
       }
       float Bv[kMaxN], Cv[kMaxN];
@@ -816,7 +815,6 @@ __global__ __launch_bounds__(64 * kSeqNW) void scan_seq_dtp_kernel(const ScanPar
 // (delta' = softplus(x) log2e, states h' = h log2e), B_t / C_t rows as scalar loads.
 // Compared with the summary / carry / final form it replaces for SGPR-eligible operands,
 // the carry never leaves the chip's LDS except for one aggregate per block.
-constexpr int kChW = 8;  // segments (waves) per workgroup
 // chunked scan, PASS 1 step loop: B|C rows fetched in pairs of steps, two steps ahead (a
 // 4-slot SGPR ring, one lgkmcnt(0) per pair): scalar loads return out of order, so a ring
 // deeper than one step needs the wait to cover whole groups.  PASS 2 keeps one row one step
@@ -827,7 +825,6 @@ constexpr int kChSPW = kMaxN / kChW;  // states a wave composes / publishes / wa
 // staged once into LDS as fp32, read per step by a broadcast ds_read one step ahead instead
 // of scalar loads (out-of-order returns, so the SGPR ring could not run deeper than a pair)
 // and their SALU unpacking
-constexpr int kChLbcRows = 256;
 constexpr int kChLbcPer = kChLbcRows * 4 / (64 * kChW);  // 16-byte row pieces per thread
 constexpr int kChPoll = kChSPW == 2 ? 8 : 4;  // preceding blocks polled per round (one-launch)
 static_assert(kMaxN % kChW == 0 && (kChSPW == 1 || kChSPW == 2), "1 or 2 states per wave");
@@ -857,7 +854,6 @@ template <int K> struct alignas(4 * K) AggShare { float v[K] = {}; };
 // first R columns zero-padded to r_pad, B = W_dt rows, v_mfma_f32_16x16x32_bf16 over
 // r_pad / 32 k-steps in order, bf16 by round-to-nearest-even), so dt is bit-identical to the
 // rows conv_proj would have written: conv_proj skips them and the scan reads x_dbl instead.
-constexpr int kChDtpT = 64;              // max segment length with dt_proj inside
 constexpr int kChDtpPitch = kChDtpT + 8;  // bf16 per channel row of a wave's dt block
 constexpr int kChDtpWPitch = 64 + 8;      // bf16 per W_dt row in LDS (r_pad <= 64)
 
@@ -1591,6 +1587,12 @@ __global__ __launch_bounds__(256) void scan_seq_carry_kernel(const ScanParams p,
   }
 }
 
+// ============================================================ host side
+// Every decision below — form, geometry, workspace layout — is taken once, by plan_scan()
+// (vm_scan_plan.h); the size queries, the support checks and the launches read its ScanPlan.
+
+static int elem_size(int dtype) { return dtype == VM_DTYPE_BF16 ? 2 : 4; }
+
 // B/C as scalar loads: 16 states, unit state stride, every row 4-byte aligned.
 static bool seq_sgpr_bc(const ScanParams& p, int es) {
   auto ok = [&](const void* ptr, long long sb, long long sn, long long sl) {
@@ -1602,143 +1604,70 @@ static bool seq_sgpr_bc(const ScanParams& p, int es) {
          span * p.b_sl < (1ll << 31) && span * p.c_sl < (1ll << 31);
 }
 
-template <typename T, int MODE, bool SP, bool HZ>
-static void launch_seq_mode(const ScanParams& p, const SeqWork& w, int segs, hipStream_t s) {
-  const int groups = (p.dim + 63) / 64;
-  dim3 grid((groups + kSeqNW - 1) / kSeqNW, segs, p.batch);
-  const bool bc1 = p.c_sl == p.b_sl && p.c_sb == p.b_sb &&
-                   static_cast<const T*>(p.C) == static_cast<const T*>(p.B) + kMaxN;
-  if constexpr (MODE == 0) {
-    if (p.split < p.batch) {  // paired: scalar B/C single pass only (seq_pair_supported)
-      if (bc1)
-        hipLaunchKernelGGL((scan_seq_kernel<T, kSeqNW, 0, SP, HZ, true, true, true, true>), grid,
-                           dim3(64 * kSeqNW), 0, s, p, w);
-      else
-        hipLaunchKernelGGL((scan_seq_kernel<T, kSeqNW, 0, SP, HZ, true, true, false, true>),
-                           grid, dim3(64 * kSeqNW), 0, s, p, w);
-      return;
-    }
-  }
-  if (seq_sgpr_bc(p, sizeof(T))) {
-    // BC1: C directly follows B in one row (the mixer's x_dbl): one scalar load for both
-    if (bc1)
-      hipLaunchKernelGGL((scan_seq_kernel<T, kSeqNW, MODE, SP, HZ, true, true, true>), grid,
-                         dim3(64 * kSeqNW), 0, s, p, w);
-    else
-      hipLaunchKernelGGL((scan_seq_kernel<T, kSeqNW, MODE, SP, HZ, true, true>), grid,
-                         dim3(64 * kSeqNW), 0, s, p, w);
-  } else {
-    hipLaunchKernelGGL((scan_seq_kernel<T, kSeqNW, MODE, SP, HZ, false, false>), grid,
-                       dim3(64 * kSeqNW), 0, s, p, w);
-  }
+// BC1: C directly follows B in one row (the mixer's x_dbl): one scalar load for both
+static bool seq_bc1(const ScanParams& p, int es) {
+  return p.c_sl == p.b_sl && p.c_sb == p.b_sb &&
+         static_cast<const char*>(p.C) == static_cast<const char*>(p.B) + kMaxN * es;
 }
 
-template <typename T, bool SP, bool HZ>
-static void launch_seq_t(const ScanParams& p, const SeqWork& w, hipStream_t s) {
-  if (w.S <= 1) {
-    launch_seq_mode<T, 0, SP, HZ>(p, w, 1, s);
-    return;
-  }
-  launch_seq_mode<T, 1, SP, HZ>(p, w, w.S - 1, s);  // the last segment's summary is unused
-  const long long total = static_cast<long long>(p.batch) * p.dim * kMaxN;
-  hipLaunchKernelGGL(scan_seq_carry_kernel, dim3(static_cast<unsigned>((total + 255) / 256)),
-                     dim3(256), 0, s, p, w);
-  launch_seq_mode<T, 2, SP, HZ>(p, w, w.S, s);
-}
-
-template <typename T>
-static void launch_seq(const ScanParams& p, const SeqWork& w, hipStream_t s) {
-  const bool hz = p.z != nullptr;
-  if (p.softplus) {
-    if (hz) launch_seq_t<T, true, true>(p, w, s);
-    else launch_seq_t<T, true, false>(p, w, s);
-  } else {
-    if (hz) launch_seq_t<T, false, true>(p, w, s);
-    else launch_seq_t<T, false, false>(p, w, s);
-  }
+// Run-time bools as template arguments: with_bools(f, a, b) calls
+// f(std::bool_constant<a>{}, std::bool_constant<b>{}) on a generic lambda f.
+template <typename F>
+static void with_bools(F&& f) { f(); }
+template <typename F, typename... Bs>
+static void with_bools(F&& f, bool b, Bs... rest) {
+  if (b) with_bools([&](auto... cs) { f(std::true_type{}, cs...); }, rest...);
+  else with_bools([&](auto... cs) { f(std::false_type{}, cs...); }, rest...);
 }
 
 // (vmhost::device_cus: 0 when it cannot be queried — no device: the size queries then
 // assume kCalibCUs)
 using vmhost::device_cus;
-
-static constexpr int kCalibCUs = 256;  // the part the cost model below was swept on
 static int cus_or_calib(int cus) { return cus > 0 ? cus : kCalibCUs; }
 
-// Segment count.  A chip-filling batch (>= 1,280 waves of 64-channel groups) runs
-// single-pass.  Below that the chunked form's time is modelled from a sweep of forced
-// segment counts at M-16f geometry (scripts/diag/scan_segments_sweep.py, B = 1 .. 64,
-// L = 3,137 and 12,545; profiles/r02_scan_segments_sweep.jsonl):
-//   time ~ 16.6 us + 0.69 us x k x T + 0.43 us x nblk
-// with T steps per segment, nblk = blocks of kChW segments per sequence and
-// k = ceil(workgroups / 256): a CU holding k of the 512-thread workgroups runs their waves'
-// steps k-fold interleaved (the passes are issue-bound), and every block adds one aggregate
-// to the entry walk.  The model is within ~6 % of the sweep; the round-1 rule (a fixed
-// ~1,792-wave target) picked 2-3x slower counts at B >= 4 (T = 126 .. 1,569 steps).
-// Depends on (batch, dim, seqlen) and the device's CU count only (the sweep ran on a
-// 256-CU MI355X; `cus` rescales k and the chip-filling threshold for other parts).
-static int choose_segments(int batch, int dim, int seqlen, int cus) {
-  if (seqlen < 64) return 1;
-  const long long groups = (dim + 63) / 64;
-  if (batch * groups >= 5 * cus) return 1;
-  const int max_s = (seqlen + 7) / 8;  // segments of at least 8 steps
-  int best = 1;
-  double best_cost = 1e30;
-  for (int S = 2; S <= max_s && S <= 2048; S += (S < 64 ? 1 : 8)) {
-    const int T = (seqlen + S - 1) / S;
-    const int segs = (seqlen + T - 1) / T;
-    const long long nblk = (segs + kChW - 1) / kChW;
-    const long long k = (batch * groups * nblk + cus - 1) / cus;
-    const double cost = 0.69 * static_cast<double>(k * T) + 0.43 * static_cast<double>(nblk);
-    if (cost < best_cost) {
-      best_cost = cost;
-      best = S;
-    }
-  }
-  return best;
+// The stream's device decides the segment count and whether the grid is co-resident.
+ScanPlan seq_plan(const ScanParams& p, int dtype, int segments, bool pair, bool dtp,
+                  size_t workspace_bytes, size_t sync_bytes, hipStream_t s) {
+  ScanPlanIn in{};
+  in.batch = p.batch; in.dim = p.dim; in.seqlen = p.seqlen; in.segments = segments;
+  in.es = elem_size(dtype);
+  in.sgpr_bc = seq_sgpr_bc(p, in.es); in.bc1 = seq_bc1(p, in.es); in.pair = pair; in.dtp = dtp;
+  in.dev_cus = device_cus(s);
+  in.cus = cus_or_calib(in.dev_cus);
+  in.ws_offer = workspace_bytes; in.sync_offer = sync_bytes;
+  return plan_scan(in);
 }
 
-// segments > 0 (an explicit ABI argument: tests and sweeps) forces the segment count;
-// 0 lets the cost model choose.
-// `cus` = the launch device's CU count (0: the current device's, or kCalibCUs).
-static int segments_for(int batch, int dim, int seqlen, int segments, int cus = 0) {
-  if (cus <= 0) cus = cus_or_calib(device_cus(nullptr));
-  int S = segments > 0 ? segments : choose_segments(batch, dim, seqlen, cus);
-  if (S > seqlen) S = seqlen > 0 ? seqlen : 1;
-  return S < 1 ? 1 : S;
+// The size queries see no operands and no buffers: the plan of operands that take the
+// chunked form with everything on offer, for the current device.
+static ScanPlan query_plan(int batch, int dim, int seqlen, int segments) {
+  ScanPlanIn in{};
+  in.batch = batch; in.dim = dim; in.seqlen = seqlen; in.segments = segments;
+  in.es = 2;
+  in.sgpr_bc = in.bc1 = true;
+  in.cus = cus_or_calib(device_cus(nullptr));
+  in.ws_offer = in.sync_offer = ~static_cast<size_t>(0);
+  return plan_scan(in);
 }
 
-// Chunked-form geometry for S segments: T steps per segment, nblk blocks of kChW segments.
-static void chunk_geometry(int seqlen, int S, int* T, int* nblk) {
-  *T = (seqlen + S - 1) / S;
-  const int segs = (seqlen + *T - 1) / *T;
-  *nblk = (segs + kChW - 1) / kChW;
+size_t seq_workspace_bytes(int batch, int dim, int seqlen, int segments) {
+  return query_plan(batch, dim, seqlen, segments).ws_query;
 }
 
-static size_t chunk_bytes(int batch, int dim, int seqlen, int S) {
-  int T, nblk;
-  chunk_geometry(seqlen, S, &T, &nblk);
-  const size_t per_blk = static_cast<size_t>(kChW + 1) * dim * (kMaxN + 1);
-  return static_cast<size_t>(batch) * nblk * per_blk * sizeof(float);
+// The header words (vm_scan.h), then one 8-byte {tag, value} granule per (row, channel
+// group, block, state | delta sum, channel).
+size_t seq_sync_bytes(int batch, int dim, int seqlen, int segments) {
+  return query_plan(batch, dim, seqlen, segments).sync_query;
 }
 
-static size_t legacy_bytes(int batch, int dim, int S) {
-  if (S > kMaxSeg) S = kMaxSeg;
-  return static_cast<size_t>(batch) * S * dim * (2 * kMaxN + 1) * sizeof(float);
-}
-
-size_t seq_workspace_bytes(int batch, int dim, int seqlen, int segments, int* chosen,
-                           int cus) {
-  const int S = segments_for(batch, dim, seqlen, segments, cus);
-  if (chosen) *chosen = S;
-  if (S <= 1) return 0;
-  const size_t a = chunk_bytes(batch, dim, seqlen, S), b = legacy_bytes(batch, dim, S);
-  return a > b ? a : b;
+int seq_chunk_steps(int batch, int dim, int seqlen, int segments) {
+  const ScanPlan pl = query_plan(batch, dim, seqlen, segments);
+  return pl.chunked() ? pl.T : 0;
 }
 
 bool seq_supported(const ScanParams& p, int dtype) {
   // buffer offsets are 31-bit byte offsets from each batch row's base
-  const long long es = dtype == VM_DTYPE_BF16 ? 2 : 4;
+  const long long es = elem_size(dtype);
   const long long span = static_cast<long long>(p.out_len > p.seqlen ? p.out_len : p.seqlen) + 1;
   auto fits = [&](long long sl) { return sl >= 0 && (span * sl + p.dim) * es < (1ll << 30); };
   return p.u_sd == 1 && p.dl_sd == 1 && p.o_sd == 1 && (p.z == nullptr || p.z_sd == 1) &&
@@ -1746,13 +1675,77 @@ bool seq_supported(const ScanParams& p, int dtype) {
          (p.z == nullptr || fits(p.z_sl));
 }
 
+static SeqWork seq_work(const ScanPlan& pl, void* workspace) {
+  SeqWork w{};
+  w.S = pl.S;
+  w.seg_len = pl.seg_len;
+  if (pl.form == ScanForm::kLegacy) {
+    float* ws = static_cast<float*>(workspace);
+    w.hend = ws + pl.hend;
+    w.hin = ws + pl.hin;
+    w.sdel = ws + pl.sdel;
+  }
+  return w;
+}
+
+static ChunkWork chunk_work(const ScanPlan& pl, void* workspace, void* sync) {
+  ChunkWork w{};
+  float* ws = static_cast<float*>(workspace);
+  w.segE = ws + pl.segE;
+  w.segP = ws + pl.segP;
+  w.aggH = ws + pl.aggH;
+  w.aggS = ws + pl.aggS;
+  w.T = pl.T;
+  w.nblk = pl.nblk;
+  if (pl.form == ScanForm::kChunk1) {
+    w.err = static_cast<unsigned*>(sync);
+    w.epoch = w.err + 1;
+    w.done = w.err + 2;
+    w.gran = reinterpret_cast<unsigned long long*>(w.err + kSyncHeaderWords);
+  }
+  return w;
+}
+
+template <typename T, int MODE, bool SP, bool HZ, bool SB = false, bool BC1 = false,
+          bool PAIR = false>
+static void launch_seq_kernel(const ScanParams& p, const SeqWork& w, int segs, hipStream_t s) {
+  const int groups = (p.dim + 63) / 64;
+  const dim3 grid((groups + kSeqNW - 1) / kSeqNW, segs, p.batch);
+  hipLaunchKernelGGL((scan_seq_kernel<T, MODE, SP, HZ, SB, BC1, PAIR>), grid, dim3(64 * kSeqNW),
+                     0, s, p, w);
+}
+
+// The single pass (w.S == 1) or the legacy summary / carry / final form.  A paired scan
+// gets here with scalar-load operands only (seq_pair_supported).
+template <typename T>
+static void launch_seq(const ScanParams& p, const SeqWork& w, hipStream_t s) {
+  with_bools([&](auto sp, auto hz) {
+    constexpr bool SP = decltype(sp)::value, HZ = decltype(hz)::value;
+    if (w.S > 1) {
+      launch_seq_kernel<T, 1, SP, HZ>(p, w, w.S - 1, s);  // the last segment's summary is unused
+      const long long total = static_cast<long long>(p.batch) * p.dim * kMaxN;
+      hipLaunchKernelGGL(scan_seq_carry_kernel, dim3(static_cast<unsigned>((total + 255) / 256)),
+                         dim3(256), 0, s, p, w);
+      launch_seq_kernel<T, 2, SP, HZ>(p, w, w.S, s);
+    } else if (seq_sgpr_bc(p, sizeof(T))) {
+      with_bools([&](auto bc1, auto pair) {
+        launch_seq_kernel<T, 0, SP, HZ, true, decltype(bc1)::value, decltype(pair)::value>(
+            p, w, 1, s);
+      }, seq_bc1(p, sizeof(T)), p.split < p.batch);
+    } else {
+      launch_seq_kernel<T, 0, SP, HZ>(p, w, 1, s);
+    }
+  }, p.softplus != 0, p.z != nullptr);
+}
+
+// lbc (ScanPlan::lbc): the block's B|C rows fit the LDS staging block
 template <typename T, bool SP, bool HZ, bool BC1, bool PAIR, bool DTP = false>
-static void launch_chunk_p(const ScanParams& p, const ChunkWork& w, hipStream_t s,
+static void launch_chunk_p(const ScanParams& p, const ChunkWork& w, bool lbc, hipStream_t s,
                            const DtpArgs& q = DtpArgs{}) {
   dim3 grid((p.dim + 63) / 64, w.nblk, p.batch);
   if (w.gran) {  // one launch: blocks hand their aggregates on through the sync buffer
     if constexpr (DTP && BC1 && sizeof(T) == 2) {
-      if (kChW * w.T <= kChLbcRows) {  // the block's B|C rows fit the LDS staging block
+      if (lbc) {
         hipLaunchKernelGGL((scan_chunk_kernel<T, 3, SP, HZ, BC1, PAIR, DTP, true>), grid,
                            dim3(64 * kChW), 0, s, p, w, q);
         return;
@@ -1768,100 +1761,36 @@ static void launch_chunk_p(const ScanParams& p, const ChunkWork& w, hipStream_t 
                      s, p, w, q);
 }
 
-template <typename T, bool SP, bool HZ, bool BC1>
-static void launch_chunk_t(const ScanParams& p, const ChunkWork& w, hipStream_t s) {
-  if (p.split < p.batch) launch_chunk_p<T, SP, HZ, BC1, true>(p, w, s);
-  else launch_chunk_p<T, SP, HZ, BC1, false>(p, w, s);
-}
-
 template <typename T>
 static void launch_chunk(const ScanParams& p, const ChunkWork& w, hipStream_t s) {
-  const bool hz = p.z != nullptr;
-  const bool bc1 = p.c_sl == p.b_sl && p.c_sb == p.b_sb &&
-                   static_cast<const T*>(p.C) == static_cast<const T*>(p.B) + kMaxN;
-#define VM_CH(SPV, HZV)                                              \
-  if (bc1) launch_chunk_t<T, SPV, HZV, true>(p, w, s);               \
-  else launch_chunk_t<T, SPV, HZV, false>(p, w, s);
-  if (p.softplus) {
-    if (hz) { VM_CH(true, true) } else { VM_CH(true, false) }
-  } else {
-    if (hz) { VM_CH(false, true) } else { VM_CH(false, false) }
-  }
-#undef VM_CH
+  with_bools([&](auto sp, auto hz, auto bc1, auto pair) {
+    launch_chunk_p<T, decltype(sp)::value, decltype(hz)::value, decltype(bc1)::value,
+                   decltype(pair)::value>(p, w, false, s);
+  }, p.softplus != 0, p.z != nullptr, seq_bc1(p, sizeof(T)), p.split < p.batch);
 }
 
-// One-launch chunked form: the sticky error word (word 0), the epoch (word 1: the tag of the
-// last launch that used the buffer) and the launch's start count (word 2), word 3 pad, then
-// one 8-byte {tag, value} granule per (row, channel group, block, state | delta sum,
-// channel).  Used when the caller passes a zeroed sync buffer this large and the whole grid
-// fits one workgroup per CU (so every block it waits on is resident).
-size_t seq_sync_bytes(int batch, int dim, int seqlen, int segments, int cus) {
-  const int S = segments_for(batch, dim, seqlen, segments, cus);
-  if (S <= 1) return 0;
-  int T, nblk;
-  chunk_geometry(seqlen, S, &T, &nblk);
-  const size_t groups = (dim + 63) / 64;
-  return kSyncHeaderWords * sizeof(unsigned) +
-         static_cast<size_t>(batch) * groups * nblk * (kMaxN + 1) * 64 * sizeof(unsigned long long);
+bool seq_pair_supported(const ScanParams& p, int dtype, const ScanPlan& pl) {
+  return seq_sgpr_bc(p, elem_size(dtype)) && (pl.chosen <= 1 || pl.chunked());
 }
 
-bool seq_pair_supported(const ScanParams& p, int dtype, int segments, size_t workspace_bytes) {
-  int S = 1;
-  const size_t need = seq_workspace_bytes(p.batch, p.dim, p.seqlen, segments, &S);
-  return seq_sgpr_bc(p, dtype == VM_DTYPE_BF16 ? 2 : 4) && (S <= 1 || workspace_bytes >= need);
-}
-
-void seq_launch(const ScanParams& p, int dtype, int segments, void* workspace,
-                size_t workspace_bytes, void* sync, size_t sync_bytes, hipStream_t s) {
-  // the stream's device decides the segment count and whether the grid is co-resident
-  const int dev_cus = device_cus(s);
-  const int cus = cus_or_calib(dev_cus);
-  int S = 1;
-  const size_t need = seq_workspace_bytes(p.batch, p.dim, p.seqlen, segments, &S, cus);
-  const int es = dtype == VM_DTYPE_BF16 ? 2 : 4;
-  if (S > 1 && workspace && workspace_bytes >= need && seq_sgpr_bc(p, es)) {
-    ChunkWork w{};
-    chunk_geometry(p.seqlen, S, &w.T, &w.nblk);
-    const long long grid = static_cast<long long>((p.dim + 63) / 64) * w.nblk * p.batch;
-    if (sync && sync_bytes >= seq_sync_bytes(p.batch, p.dim, p.seqlen, segments, cus) &&
-        grid <= dev_cus) {
-      w.err = static_cast<unsigned*>(sync);
-      w.epoch = w.err + 1;
-      w.done = w.err + 2;
-      w.gran = reinterpret_cast<unsigned long long*>(w.err + kSyncHeaderWords);
-    }
-    const size_t nb = static_cast<size_t>(p.batch) * w.nblk;
-    w.segE = static_cast<float*>(workspace);
-    w.segP = w.segE + nb * kChW * p.dim * kMaxN;
-    w.aggH = w.segP + nb * kChW * p.dim;
-    w.aggS = w.aggH + nb * p.dim * kMaxN;
+void seq_launch(const ScanParams& p, int dtype, const ScanPlan& pl, void* workspace, void* sync,
+                hipStream_t s) {
+  if (pl.chunked()) {
+    const ChunkWork w = chunk_work(pl, workspace, sync);
     if (dtype == VM_DTYPE_BF16) launch_chunk<bf16_t>(p, w, s);
     else launch_chunk<float>(p, w, s);
     return;
   }
-  SeqWork w{};
-  if (S > kMaxSeg) S = kMaxSeg;
-  if (S > 1 && workspace && workspace_bytes >= need) {
-    const size_t states = static_cast<size_t>(p.batch) * S * p.dim * kMaxN;
-    w.hend = static_cast<float*>(workspace);
-    w.hin = w.hend + states;
-    w.sdel = w.hin + states;
-    w.seg_len = (p.seqlen + S - 1) / S;
-    w.S = (p.seqlen + w.seg_len - 1) / w.seg_len;  // every segment non-empty
-  } else {
-    w.S = 1;
-    w.seg_len = p.seqlen;
-  }
+  const SeqWork w = seq_work(pl, workspace);
   if (dtype == VM_DTYPE_BF16) launch_seq<bf16_t>(p, w, s);
   else launch_seq<float>(p, w, s);
 }
 
 bool seq_dtp_supported(const ScanParams& p, const DtpArgs& q, int dtype, int dt_rank) {
-  const bool bc1 = p.c_sl == p.b_sl && p.c_sb == p.b_sb &&
-                   static_cast<const bf16_t*>(p.C) == static_cast<const bf16_t*>(p.B) + kMaxN;
   const int nks = (dt_rank + 15) / 16;
   const long long dl_span = static_cast<long long>(p.out_len) * q.dtl_sl * 2;
-  return dtype == VM_DTYPE_BF16 && seq_supported(p, dtype) && seq_sgpr_bc(p, 2) && bc1 &&
+  return dtype == VM_DTYPE_BF16 && seq_supported(p, dtype) && seq_sgpr_bc(p, 2) &&
+         seq_bc1(p, 2) &&
          p.dstate == kMaxN && p.z && p.softplus && p.split == p.batch &&
          p.dim % (64 * kSeqNW) == 0 && dt_rank >= 1 && dt_rank <= 64 && dt_rank % 4 == 0 &&
          q.dt_rank == dt_rank && q.dtl && q.wdt &&
@@ -1872,30 +1801,13 @@ bool seq_dtp_supported(const ScanParams& p, const DtpArgs& q, int dtype, int dt_
          static_cast<long long>(p.seqlen) * q.dtl_sl * 2 < (1ll << 31);
 }
 
-// Segment length the chunked form would run (0 = the single pass), for the host's choice of
-// dt_proj placement (inside the chunked scan up to kChDtpT steps).
-int seq_chunk_steps(int batch, int dim, int seqlen, int segments) {
-  const int S = segments_for(batch, dim, seqlen, segments, cus_or_calib(device_cus(nullptr)));
-  if (S <= 1) return 0;
-  int T, nblk;
-  chunk_geometry(seqlen, S, &T, &nblk);
-  return T;
-}
-
 // dt_proj inside the chunked scan (DTP): the mixer's bf16 token-major operands with the
-// conv_proj-form W_dt (r_pad = 32 or 64 columns) and segments of at most kChDtpT steps.
-bool seq_dtp_chunk_supported(const ScanParams& p, const DtpArgs& q, int dtype, int segments,
-                             size_t workspace_bytes) {
-  const bool bc1 = p.c_sl == p.b_sl && p.c_sb == p.b_sb &&
-                   static_cast<const bf16_t*>(p.C) == static_cast<const bf16_t*>(p.B) + kMaxN;
-  int S = 1;
-  const size_t need = seq_workspace_bytes(p.batch, p.dim, p.seqlen, segments, &S);
-  if (S <= 1) return false;
-  int T, nblk;
-  chunk_geometry(p.seqlen, S, &T, &nblk);
-  return dtype == VM_DTYPE_BF16 && seq_supported(p, dtype) && seq_sgpr_bc(p, 2) && bc1 &&
-         p.dstate == kMaxN && p.z && p.softplus && p.split == p.batch && T <= kChDtpT &&
-         workspace_bytes >= need &&
+// conv_proj-form W_dt (r_pad = 32 or 64 columns); `pl` (planned with dtp) is chunked only
+// for scalar-load B|C rows, segments of at most kChDtpT steps and enough workspace.
+bool seq_dtp_chunk_supported(const ScanParams& p, const DtpArgs& q, int dtype,
+                             const ScanPlan& pl) {
+  return dtype == VM_DTYPE_BF16 && seq_supported(p, dtype) && pl.chunked() &&
+         p.dstate == kMaxN && p.z && p.softplus && p.split == p.batch &&
          q.dtl && q.wdt && (q.wdt_ld == 32 || q.wdt_ld == 64) && q.dt_rank >= 1 &&
          q.dt_rank <= q.wdt_ld && q.dt_rank % 4 == 0 && q.dtl_sl >= q.dt_rank &&
          (reinterpret_cast<uintptr_t>(q.dtl) & 7) == 0 && q.dtl_sl % 4 == 0 && q.dtl_sb % 4 == 0 &&
@@ -1903,28 +1815,10 @@ bool seq_dtp_chunk_supported(const ScanParams& p, const DtpArgs& q, int dtype, i
          static_cast<long long>(p.out_len) * q.dtl_sl * 2 < (1ll << 31);
 }
 
-void seq_dtp_chunk_launch(const ScanParams& p, const DtpArgs& q, int segments, void* workspace,
-                          size_t workspace_bytes, void* sync, size_t sync_bytes, hipStream_t s) {
-  const int dev_cus = device_cus(s);
-  const int cus = cus_or_calib(dev_cus);
-  int S = 1;
-  seq_workspace_bytes(p.batch, p.dim, p.seqlen, segments, &S, cus);
-  ChunkWork w{};
-  chunk_geometry(p.seqlen, S, &w.T, &w.nblk);
-  const long long grid = static_cast<long long>((p.dim + 63) / 64) * w.nblk * p.batch;
-  if (sync && sync_bytes >= seq_sync_bytes(p.batch, p.dim, p.seqlen, segments, cus) &&
-      grid <= dev_cus) {
-    w.err = static_cast<unsigned*>(sync);
-    w.epoch = w.err + 1;
-    w.done = w.err + 2;
-    w.gran = reinterpret_cast<unsigned long long*>(w.err + kSyncHeaderWords);
-  }
-  const size_t nb = static_cast<size_t>(p.batch) * w.nblk;
-  w.segE = static_cast<float*>(workspace);
-  w.segP = w.segE + nb * kChW * p.dim * kMaxN;
-  w.aggH = w.segP + nb * kChW * p.dim;
-  w.aggS = w.aggH + nb * p.dim * kMaxN;
-  launch_chunk_p<bf16_t, true, true, true, false, true>(p, w, s, q);
+void seq_dtp_chunk_launch(const ScanParams& p, const DtpArgs& q, const ScanPlan& pl,
+                          void* workspace, void* sync, hipStream_t s) {
+  launch_chunk_p<bf16_t, true, true, true, false, true>(p, chunk_work(pl, workspace, sync),
+                                                        pl.lbc, s, q);
 }
 
 void seq_dtp_launch(const ScanParams& p, const DtpArgs& q, int dt_rank, hipStream_t s) {

@@ -246,6 +246,28 @@ def scan_workspace_bytes(batch: int, dim: int, seqlen: int, dstate: int,
     return int(_lib.load().vm_selective_scan_workspace_bytes(batch, dim, seqlen, dstate, seg))
 
 
+def _scan_buffers(device, stream, batch, dim, seqlen, dstate, workspace: Optional[Tensor]):
+    """``(seg, ws, ws_bytes, sync, sync_bytes)`` of a token-major scan launch: the segment
+    option, the workspace the library asks for (``workspace`` or the per-stream scratch) and,
+    for a segmented scan under ``scan_one_launch``, the sync buffer."""
+    seg = int(options.get().scan_segments)
+    ws_bytes = scan_workspace_bytes(batch, dim, seqlen, dstate, seg)
+    ws, sync, sync_bytes = None, None, 0
+    if ws_bytes:
+        if workspace is not None:
+            if workspace.numel() < ws_bytes:
+                raise ValueError(f"scan workspace too small: {workspace.numel()} < {ws_bytes}")
+            ws = workspace
+        else:
+            ws = scratch(device, int(stream), ws_bytes)
+        if options.get().scan_one_launch:
+            sync_bytes = scan_sync_bytes(batch, dim, seqlen, dstate, seg)
+            sync = sync_buffer(device, int(stream), sync_bytes)
+            if sync is None:
+                sync_bytes = 0
+    return seg, ws, ws_bytes, sync, sync_bytes
+
+
 def scan_raw(u, u_s, delta, dl_s, A32, B, b_s, C, c_s, D32, z, z_s, bias32, softplus,
              h0, h0_s, h_last, hl_s, out, o_s, out_len, batch, dim, seqlen, dstate, dtype,
              stream, workspace: Optional[Tensor] = None, pair=None):
@@ -255,23 +277,10 @@ def scan_raw(u, u_s, delta, dl_s, A32, B, b_s, C, c_s, D32, z, z_s, bias32, soft
     ``pair`` = (split, A32_bwd, D32_bwd, bias32_bwd, h0_bwd, h_last_bwd, frame_len) runs
     ``vm_selective_scan_bidir_fwd``: rows >= split are the flipped backward direction."""
     lib = _lib.load()
-    seg = int(options.get().scan_segments)
-    ws_bytes = 0
-    ws = None
-    sync, sync_bytes = None, 0
+    seg, ws, ws_bytes, sync, sync_bytes = int(options.get().scan_segments), None, 0, None, 0
     if u_s[1] == 1:
-        ws_bytes = scan_workspace_bytes(batch, dim, seqlen, dstate, seg)
-        if workspace is not None:
-            if workspace.numel() < ws_bytes:
-                raise ValueError(f"scan workspace too small: {workspace.numel()} < {ws_bytes}")
-            ws = workspace
-        else:
-            ws = scratch(u.device, int(stream), ws_bytes)
-        if options.get().scan_one_launch:
-            sync_bytes = scan_sync_bytes(batch, dim, seqlen, dstate, seg)
-            sync = sync_buffer(u.device, int(stream), sync_bytes)
-            if sync is None:
-                sync_bytes = 0
+        seg, ws, ws_bytes, sync, sync_bytes = _scan_buffers(u.device, stream, batch, dim, seqlen,
+                                                            dstate, workspace)
     args = (_p(u), u_s[0], u_s[1], u_s[2], _p(delta), dl_s[0], dl_s[1], dl_s[2], _p(A32),
             _p(B), b_s[0], b_s[1], b_s[2], _p(C), c_s[0], c_s[1], c_s[2],
             _p(D32), _p(z), z_s[0], z_s[1], z_s[2], _p(bias32), int(softplus),
@@ -298,7 +307,7 @@ def scan_chunk_steps(batch: int, dim: int, seqlen: int, dstate: int, segments: i
 
 
 SCAN_DTPROJ_MAX_SEGMENT = 64  # the segmented dt_proj-in-scan form (ABI v11)
-_SCAN_CHUNK_SEGS_PER_BLOCK = 8  # segments per workgroup of the chunked scan (kChW)
+_SCAN_CHUNK_SEGS_PER_BLOCK = 8  # segments per workgroup of the chunked scan (vm_scan_plan.h kChW)
 _CU_COUNT = {}
 
 
@@ -338,21 +347,8 @@ def scan_dtproj_raw(u, u_s, dtl, dtl_s, dt_rank, wdt_pad, A32, B, b_s, C, c_s, D
     the segmented form (segments of at most 64 steps) computes each segment's dt exactly as
     conv_proj's dt_proj would (ABI v11), with the scratch / sync buffers of ``scan_raw``."""
     lib = _lib.load()
-    seg = int(options.get().scan_segments)
-    ws_bytes = scan_workspace_bytes(batch, dim, seqlen, dstate, seg)
-    ws, sync, sync_bytes = None, None, 0
-    if ws_bytes:
-        if workspace is not None:
-            if workspace.numel() < ws_bytes:
-                raise ValueError(f"scan workspace too small: {workspace.numel()} < {ws_bytes}")
-            ws = workspace
-        else:
-            ws = scratch(u.device, int(stream), ws_bytes)
-        if options.get().scan_one_launch:
-            sync_bytes = scan_sync_bytes(batch, dim, seqlen, dstate, seg)
-            sync = sync_buffer(u.device, int(stream), sync_bytes)
-            if sync is None:
-                sync_bytes = 0
+    seg, ws, ws_bytes, sync, sync_bytes = _scan_buffers(u.device, stream, batch, dim, seqlen,
+                                                        dstate, workspace)
     rc = lib.vm_selective_scan_dtproj_fwd(
         _p(u), u_s[0], u_s[1], u_s[2], _p(dtl), dtl_s[0], dtl_s[1], int(dt_rank),
         _p(wdt_pad), wdt_pad.stride(0), _p(A32),

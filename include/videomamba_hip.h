@@ -9,6 +9,8 @@
  *                                 (models/videomamba/mamba_simple.py:122-152, stateless and
  *                                  initial_state forms; also replaces the per-token
  *                                  selective_state_update loop at :153-172)
+ *   vm_selective_scan_bwd      <- the backward of mamba_ssm selective_scan_fn
+ *                                 (mamba_simple.py:122-152 under autograd)
  *   vm_selective_scan_dtproj_fwd <- dt_proj (mamba_simple.py:409-413) + selective_scan_fn,
  *                                 dt computed inside the scan on the matrix cores
  *   vm_selective_scan_bidir_fwd <- the forward + flipped backward scans of
@@ -60,7 +62,7 @@
 extern "C" {
 #endif
 
-#define VM_ABI_VERSION 14
+#define VM_ABI_VERSION 15
 
 #define VM_DTYPE_F32 0
 #define VM_DTYPE_BF16 1
@@ -212,6 +214,55 @@ long long vm_selective_scan_sync_bytes(int batch, int dim, int seqlen, int dstat
  * bytes of the device buffer.  Returns 0 (no hand-off ever timed out), 1 (some launch timed
  * out: its outputs are NaN), or VM_E_INVALID.  Pure host code (no HIP call). */
 int vm_selective_scan_sync_status(const void* sync_host, long long bytes);
+
+/*
+ * Selective scan backward (ABI v15): the gradient of vm_selective_scan_fwd, what mamba_ssm's
+ * differentiable selective_scan_fn supplies at mamba_simple.py:122-152.  u, delta, A, B, C,
+ * D, z, delta_bias, delta_softplus and h0 are the forward's inputs, passed exactly as to
+ * vm_selective_scan_fwd; nothing the forward computed is needed.
+ *   dout:    (batch, dim, seqlen) in `dtype`, the gradient of out;
+ *   dh_last: (batch, dim, dstate) fp32 strides (sb, sd, 1), the gradient of the forward's
+ *            last state, NULL = 0.
+ * Outputs, every one overwritten (never accumulated into):
+ *   du, ddelta, dz: (batch, dim, seqlen) in `dtype` (dz NULL iff z NULL);
+ *   dB, dC:  (batch, dstate, seqlen) in `dtype`, any strides;
+ *   dA:      (dim, dstate) fp32 contiguous;  dD, ddelta_bias: (dim) fp32 (NULL iff D /
+ *            delta_bias NULL);  dh0: (batch, dim, dstate) fp32 strides (sb, sd, 1), nullable.
+ * Token-major operands only: unit channel stride for u / delta / z / dout / du / ddelta / dz,
+ * unit state stride for B / C, dstate == 16; fp32 or bf16 with all arithmetic in fp32 and
+ * bf16 gradients rounded once at the store.  Anything else (a null required pointer, another
+ * dtype, a workspace below vm_selective_scan_bwd_workspace_bytes) returns VM_E_INVALID before
+ * any launch.  One workgroup per (batch row, 64 channels) walks the sequence step by step; a
+ * batch of a few rows leaves most of the chip idle (there is no time-segmented backward).
+ * Deterministic: no atomics; the cross-channel sums (dB, dC) and the batch sums (dA, dD,
+ * ddelta_bias) go through fp32 partials in the workspace, added in a fixed order.
+ */
+int vm_selective_scan_bwd(const void* u, long long u_sb, long long u_sd, long long u_sl,
+                          const void* delta, long long dl_sb, long long dl_sd, long long dl_sl,
+                          const float* A,
+                          const void* B, long long b_sb, long long b_sn, long long b_sl,
+                          const void* C, long long c_sb, long long c_sn, long long c_sl,
+                          const float* D, const void* z, long long z_sb, long long z_sd,
+                          long long z_sl, const float* delta_bias, int delta_softplus,
+                          const void* h0, int h0_dtype, long long h0_sb, long long h0_sd,
+                          const void* dout, long long do_sb, long long do_sd, long long do_sl,
+                          const float* dh_last, long long dhl_sb, long long dhl_sd,
+                          void* du, long long du_sb, long long du_sd, long long du_sl,
+                          void* ddelta, long long dd_sb, long long dd_sd, long long dd_sl,
+                          void* dz, long long dz_sb, long long dz_sd, long long dz_sl,
+                          void* dB, long long dB_sb, long long dB_sn, long long dB_sl,
+                          void* dC, long long dC_sb, long long dC_sn, long long dC_sl,
+                          float* dA, float* dD, float* ddelta_bias,
+                          float* dh0, long long dh0_sb, long long dh0_sd,
+                          int batch, int dim, int seqlen, int dstate, int dtype,
+                          void* workspace, long long workspace_bytes, vm_stream_t stream);
+
+/* Workspace bytes vm_selective_scan_bwd needs for this shape (0 when dstate != 16, which the
+ * entry refuses): the states entering every 8-step chunk but the first, the per-channel-group
+ * partials of dB | dC and the per-batch-row partials of dA, dD and ddelta_bias — at most
+ * 12 batch seqlen dpad + 4 batch dpad (dstate + 2) + 4096 with dpad = round_up(dim, 64).
+ * Pure host code (no HIP call). */
+long long vm_selective_scan_bwd_workspace_bytes(int batch, int dim, int seqlen, int dstate);
 
 /*
  * One-token scan step on `state` (updated in place, own dtype; fp32 math).

@@ -20,7 +20,7 @@ LIB_PATH = os.path.join(os.path.dirname(os.path.abspath(__file__)), LIB_NAME)
 
 VM_DTYPE_F32 = 0
 VM_DTYPE_BF16 = 1
-ABI_VERSION = 14
+ABI_VERSION = 15
 
 _P = c_void_p
 _LL = c_longlong
@@ -69,6 +69,27 @@ _SIGNATURES = {
     "vm_selective_scan_workspace_bytes": ([_I, _I, _I, _I, _I], _LL),
     "vm_selective_scan_sync_bytes": ([_I, _I, _I, _I, _I], _LL),
     "vm_selective_scan_sync_status": ([_P, _LL], _I),
+    "vm_selective_scan_bwd": (
+        [_P, _LL, _LL, _LL,       # u (sb, sd, sl)
+         _P, _LL, _LL, _LL,       # delta
+         _P,                      # A
+         _P, _LL, _LL, _LL,       # B (sb, sn, sl)
+         _P, _LL, _LL, _LL,       # C
+         _P, _P, _LL, _LL, _LL,   # D, z
+         _P, _I,                  # delta_bias, softplus
+         _P, _I, _LL, _LL,        # h0
+         _P, _LL, _LL, _LL,       # dout
+         _P, _LL, _LL,            # dh_last (sb, sd)
+         _P, _LL, _LL, _LL,       # du
+         _P, _LL, _LL, _LL,       # ddelta
+         _P, _LL, _LL, _LL,       # dz
+         _P, _LL, _LL, _LL,       # dB (sb, sn, sl)
+         _P, _LL, _LL, _LL,       # dC
+         _P, _P, _P,              # dA, dD, ddelta_bias
+         _P, _LL, _LL,            # dh0 (sb, sd)
+         _I, _I, _I, _I, _I,      # batch, dim, seqlen, dstate, dtype
+         _P, _LL, _P], _I),       # workspace, bytes, stream
+    "vm_selective_scan_bwd_workspace_bytes": ([_I, _I, _I, _I], _LL),
     "vm_selective_state_update": (
         [_P, _I, _LL, _LL, _P, _LL, _P, _LL, _P, _P, _LL, _P, _LL, _P, _P, _LL, _P, _I,
          _P, _LL, _I, _I, _I, _I, _P], _I),

@@ -3,7 +3,9 @@
 Public functions keep the call shapes the reference uses for its third-party kernels
 (``models/videomamba/mamba_simple.py:11-14``, ``videomamba.py:11``):
 
-* ``selective_scan_fn``      <- mamba_ssm ``selective_scan_fn`` (+ ``initial_state``)
+* ``selective_scan_fn``      <- mamba_ssm ``selective_scan_fn`` (+ ``initial_state``),
+  differentiable: with grad mode on and an operand that requires grad it builds an autograd
+  graph whose backward is the HIP kernel ``vm_selective_scan_bwd``
 * ``selective_state_update`` <- mamba_ssm Triton ``selective_state_update``
 * ``causal_conv1d_fn`` / ``causal_conv1d_update`` <- causal-conv1d
 * ``rms_norm_fn`` / ``layer_norm_fn`` <- mamba_ssm Triton layer norm
@@ -297,6 +299,44 @@ def scan_raw(u, u_s, delta, dl_s, A32, B, b_s, C, c_s, D32, z, z_s, bias32, soft
                                          _p(hl_b), frame, seg, _p(ws), ws_bytes, _p(sync),
                                          sync_bytes, stream)
     _lib.check(rc, "vm_selective_scan_bidir_fwd")
+
+
+def scan_bwd_workspace_bytes(batch: int, dim: int, seqlen: int, dstate: int) -> int:
+    return int(_lib.load().vm_selective_scan_bwd_workspace_bytes(batch, dim, seqlen, dstate))
+
+
+def selective_scan_bwd_raw(u, u_s, delta, dl_s, A32, B, b_s, C, c_s, D32, z, z_s, bias32,
+                           softplus, h0, h0_s, dout, do_s, dh_last, dhl_s, du, du_s, ddelta,
+                           dd_s, dz, dz_s, dB, dB_s, dC, dC_s, dA, dD, dbias, dh0, dh0_s,
+                           batch, dim, seqlen, dstate, dtype, stream,
+                           workspace: Optional[Tensor] = None):
+    """``vm_selective_scan_bwd``: the gradients of :func:`scan_raw` on token-major operands
+    (unit channel stride for u / delta / z / dout / du / ddelta / dz, unit state stride for
+    B / C, 16 states).  The forward's inputs are passed as to :func:`scan_raw`; ``dout`` is
+    the gradient of its output, ``dh_last`` (fp32, nullable) that of its last state.  Every
+    gradient buffer is overwritten: du / ddelta / dz / dB / dC in ``dtype``, dA / dD / dbias /
+    dh0 fp32.  ``workspace`` (a uint8 device buffer) replaces the per-stream scratch."""
+    lib = _lib.load()
+    ws_bytes = scan_bwd_workspace_bytes(batch, dim, seqlen, dstate)
+    ws = None
+    if ws_bytes:
+        if workspace is not None:
+            if workspace.numel() < ws_bytes:
+                raise ValueError(f"scan backward workspace too small: {workspace.numel()} < "
+                                 f"{ws_bytes}")
+            ws = workspace
+        else:
+            ws = scratch(u.device, int(stream), ws_bytes)
+    s2 = lambda s: (s[0], s[1])  # noqa: E731
+    rc = lib.vm_selective_scan_bwd(
+        _p(u), *u_s, _p(delta), *dl_s, _p(A32), _p(B), *b_s, _p(C), *c_s,
+        _p(D32), _p(z), *z_s, _p(bias32), int(softplus),
+        _p(h0), dtype_code(h0.dtype) if h0 is not None else 0, *s2(h0_s),
+        _p(dout), *do_s, _p(dh_last), *s2(dhl_s),
+        _p(du), *du_s, _p(ddelta), *dd_s, _p(dz), *dz_s, _p(dB), *dB_s, _p(dC), *dC_s,
+        _p(dA), _p(dD), _p(dbias), _p(dh0), *s2(dh0_s),
+        batch, dim, seqlen, dstate, dtype, _p(ws), ws_bytes, stream)
+    _lib.check(rc, "vm_selective_scan_bwd")
 
 
 def scan_chunk_steps(batch: int, dim: int, seqlen: int, dstate: int, segments: int = -1) -> int:
@@ -650,6 +690,79 @@ def pool_finish(ws: Optional[Tensor], feats: Tensor, *, mode: str, keep_temporal
 
 
 # --------------------------------------------------------------------------- selective scan
+BWD_DSTATE = 16  # the state count vm_selective_scan_bwd takes
+
+
+def _tm_strides(t: Tensor) -> Tuple[int, int, int]:
+    """(batch, channel|state, step) element strides of a token-major (b, d, l) view; a
+    single channel's stride is immaterial and reported as 1."""
+    return (t.stride(0), 1 if t.shape[1] <= 1 else t.stride(1), t.stride(2))
+
+
+class _SelectiveScan(torch.autograd.Function):
+    """``scan_raw`` forward, ``selective_scan_bwd_raw`` backward, on token-major operands in
+    u's dtype with fp32 A / D / bias / initial state (the casts and layout changes are the
+    caller's, as ordinary differentiable torch ops)."""
+
+    @staticmethod
+    def forward(ctx, u, delta, A, B, C, D, z, bias, h0, softplus, want_last):
+        # grad mode is off in here: this is the no-grad call, same kernels, same bits
+        res = selective_scan_fn(u, delta, A, B, C, D, z, bias, softplus, want_last, h0)
+        ctx.save_for_backward(u, delta, A, B, C, D, z, bias, h0)
+        ctx.softplus = softplus
+        return res if want_last else (res, None)
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, dout, dh_last):
+        u, delta, A, B, C, D, z, bias, h0 = ctx.saved_tensors
+        batch, dim, seqlen = u.shape
+        n = A.shape[1]
+        dev = u.device
+        dout = _channel_contig(dout.to(u.dtype))
+        if dh_last is not None:
+            dh_last = dh_last.float().contiguous()
+
+        def tm_empty(ch):
+            return torch.empty((batch, seqlen, ch), dtype=u.dtype, device=dev).transpose(1, 2)
+
+        f32 = lambda *shape: torch.empty(shape, dtype=torch.float32, device=dev)  # noqa: E731
+        du, ddelta, dB, dC = tm_empty(dim), tm_empty(dim), tm_empty(n), tm_empty(n)
+        dz = tm_empty(dim) if z is not None else None
+        dA = f32(dim, n)
+        dD = f32(dim) if D is not None else None
+        dbias = f32(dim) if bias is not None else None
+        dh0 = f32(batch, dim, n) if h0 is not None else None
+        s3 = lambda t: _tm_strides(t) if t is not None else (0, 0, 0)  # noqa: E731
+        s2 = lambda t: (t.stride(0), t.stride(1)) if t is not None else (0, 0)  # noqa: E731
+        selective_scan_bwd_raw(u, s3(u), delta, s3(delta), A, B, s3(B), C, s3(C), D, z, s3(z),
+                               bias, ctx.softplus, h0, s2(h0), dout, s3(dout), dh_last,
+                               s2(dh_last), du, s3(du), ddelta, s3(ddelta), dz, s3(dz),
+                               dB, s3(dB), dC, s3(dC), dA, dD, dbias, dh0, s2(dh0),
+                               batch, dim, seqlen, n, dtype_code(u.dtype), _stream(u))
+        return du, ddelta, dA, dB, dC, dD, dz, dbias, dh0, None, None
+
+
+def _selective_scan_autograd(u, delta, A, B, C, D, z, delta_bias, delta_softplus,
+                             return_last_state, initial_state, last_state_out):
+    """The differentiable form of :func:`selective_scan_fn`: casts to u's dtype (fp32 for A,
+    D, the bias and the initial state) and token-major views as differentiable torch ops, so
+    every gradient comes back in its input's dtype and shape, then :class:`_SelectiveScan`."""
+    if last_state_out is not None:
+        raise ValueError("selective_scan_fn: last_state_out= writes the state in place, which "
+                         "has no gradient; drop it or call under torch.no_grad()")
+    if A.shape[1] != BWD_DSTATE:
+        raise NotImplementedError(f"selective_scan_fn backward takes dstate == {BWD_DSTATE}, "
+                                  f"got {A.shape[1]}")
+    dtype_code(u.dtype)
+    tm = lambda t: None if t is None else _channel_contig(t.to(u.dtype))  # noqa: E731
+    f32 = lambda t: None if t is None else t.float().contiguous()  # noqa: E731
+    out, last = _SelectiveScan.apply(tm(u), tm(delta), f32(A), tm(B), tm(C), f32(D), tm(z),
+                                     f32(delta_bias), f32(initial_state), bool(delta_softplus),
+                                     bool(return_last_state))
+    return (out, last) if return_last_state else out
+
+
 def selective_scan_fn(u: Tensor, delta: Tensor, A: Tensor, B: Tensor, C: Tensor,
                       D: Optional[Tensor] = None, z: Optional[Tensor] = None,
                       delta_bias: Optional[Tensor] = None, delta_softplus: bool = False,
@@ -682,6 +795,11 @@ def selective_scan_fn(u: Tensor, delta: Tensor, A: Tensor, B: Tensor, C: Tensor,
             last_state_out.copy_(h)
             h = last_state_out
         return out, h
+    if torch.is_grad_enabled() and any(
+            t is not None and t.requires_grad
+            for t in (u, delta, A, B, C, D, z, delta_bias, initial_state)):
+        return _selective_scan_autograd(u, delta, A, B, C, D, z, delta_bias, delta_softplus,
+                                        return_last_state, initial_state, last_state_out)
     # Layout follows u: token-major views (unit channel stride, e.g. a transposed
     # (b, l, d) tensor) take the channel-per-lane kernels, anything else is made
     # step-contiguous for the time-parallel kernels.

@@ -75,14 +75,17 @@ _warned_grad = False
 
 
 def warn_if_grad(*tensors: Optional[Tensor]) -> None:
-    """The HIP path is forward-only; say so once when autograd would expect a graph."""
+    """The model-level HIP forward builds no autograd graph; say so once when autograd would
+    expect one.  (The mixer in training mode and ``selective_scan_fn`` are differentiable.)"""
     global _warned_grad
     if _warned_grad or not torch.is_grad_enabled():
         return
     if any(t is not None and t.requires_grad for t in tensors):
         _warned_grad = True
-        warnings.warn("VideoMamba's HIP kernels are forward-only: outputs are computed "
-                      "without autograd (wrap inference in torch.no_grad()).", stacklevel=3)
+        warnings.warn("VideoMamba's model-level HIP forward is not differentiable yet: its "
+                      "outputs are computed without autograd (wrap inference in "
+                      "torch.no_grad()).  The Mamba mixer in .train() mode and "
+                      "kernels.selective_scan_fn are differentiable.", stacklevel=3)
 
 
 def round_up(n: int, m: int = 8) -> int:

@@ -30,6 +30,11 @@ and keeps the state in fp32 internally.  State semantics:
   place and returned (the reference's fallback aliases it the same way).
 * ``ssm_state=t`` alone (legacy): conv restarts from zeros, ``t`` updated in place.
 * ``inference_params``: prefill (offset 0) fills the cache; offset > 0 runs ``step``.
+
+Training: a mixer in ``.train()`` mode called with autograd on and something that requires
+grad (and neither ``inference_params`` nor the legacy ``ssm_state=``) runs
+:meth:`Mamba._forward_train`, differentiable end to end: torch ops around the HIP scan and its
+HIP backward (vm_selective_scan_bwd).  Everything else runs the inference path above unchanged.
 """
 
 from __future__ import annotations
@@ -574,9 +579,62 @@ class Mamba(nn.Module):
             raise ValueError("state is not supported with inference_params.")
         if not hidden_states.is_cuda:
             raise RuntimeError(_CUDA_ERROR)
+        if (self.training and inference_params is None and ssm_state is None
+                and torch.is_grad_enabled()
+                and (hidden_states.requires_grad
+                     or any(p.requires_grad for p in self.parameters()))):
+            return self._forward_train(hidden_states, state, return_state)
         warn_if_grad(hidden_states, self.in_proj.weight)
         with torch.no_grad():
             return self._forward(hidden_states, inference_params, ssm_state, state, return_state)
+
+    def _forward_train(self, hs: Tensor, state: Optional[Tuple[Tensor, Tensor]],
+                       return_state: bool):
+        """The differentiable mixer (``mamba_simple.py:333-451`` under autograd): the
+        projections and the 4-tap depthwise conv as torch ops, the scan and its gradient on
+        the HIP kernels (``K.selective_scan_fn``) over token-major views, rounding points as
+        the inference path.  With ``state`` the conv continues from ``conv_state`` and the
+        scan from ``ssm_state``; the returned states are new tensors attached to the graph
+        (the last ``d_conv`` raw conv inputs, the scan's fp32 last state)."""
+        Bsz, L, _ = hs.shape
+        Dm, N, R, W = self.d_inner, self.d_state, self.dt_rank, self.d_conv
+        conv_state = ssm_state = None
+        if state is not None:
+            conv_state, ssm_state = state
+            if conv_state is not None:
+                self._check_state(conv_state, W, "conv_state", Bsz)
+            if ssm_state is not None:
+                self._check_state(ssm_state, N, "ssm_state", Bsz)
+        xz = F.linear(hs, self.in_proj.weight, self.in_proj.bias)  # (B, L, 2D)
+        x, z = xz[..., :Dm], xz[..., Dm:]
+        # causal depthwise conv over [left context | x], tap by tap in fp32
+        if conv_state is not None:
+            left = conv_state.to(x.dtype).transpose(1, 2)  # (B, W, D)
+        else:
+            left = x.new_zeros((Bsz, W, Dm))
+        xin = torch.cat([left, x], dim=1)  # (B, W + L, D); tap k of step t is row t + 1 + k
+        w = self.conv1d.weight.reshape(Dm, W).float()
+        xf = xin.float()
+        acc = xf[:, 1:1 + L] * w[:, 0]
+        for k in range(1, W):
+            acc = acc + xf[:, 1 + k:1 + k + L] * w[:, k]
+        if self.conv1d.bias is not None:
+            acc = acc + self.conv1d.bias.float()
+        u = F.silu(acc).to(x.dtype)  # (B, L, D)
+        x_dbl = F.linear(u, self.x_proj.weight, self.x_proj.bias)  # (B, L, R + 2N)
+        dt = F.linear(x_dbl[..., :R], self.dt_proj.weight)  # bias added inside the scan
+        A = -torch.exp(self.A_log.float())
+        tm = lambda t: t.transpose(1, 2)  # noqa: E731  (B, L, ch) -> token-major (B, ch, L)
+        y, last = K.selective_scan_fn(
+            tm(u), tm(dt), A, tm(x_dbl[..., R:R + N]), tm(x_dbl[..., R + N:]), self.D.float(),
+            z=tm(z), delta_bias=self.dt_proj.bias.float(), delta_softplus=True,
+            initial_state=ssm_state, return_last_state=True)
+        out = F.linear(tm(y), self.out_proj.weight, self.out_proj.bias)
+        if not return_state:
+            return out
+        cs_dtype = conv_state.dtype if conv_state is not None else hs.dtype
+        new_conv = xin[:, -W:].transpose(1, 2).to(cs_dtype)  # the last d_conv raw inputs
+        return out, (new_conv, last)
 
     def _forward(self, hs, inference_params, ssm_state, state, return_state):
         batch, seqlen, dm = hs.shape

@@ -306,9 +306,10 @@ int vm_causal_conv1d_fwd(const void* x, long long x_sb, long long x_sd, long lon
  * with step >= seqlen are written as 0.  conv state as vm_causal_conv1d_fwd (width <= 4).
  * dim % 64 == 0, seqlen >= 1.
  * dt == NULL skips dt_proj (conv + x_proj only; wdt_pad may then be NULL too).
- * batch <= 8 runs a split-K form (fixed 128-channel splits of the x_proj reduction, so
+ * batch <= 8 (with dt_softplus == 0, dim <= 2048, round_up(e, 4) <= 76 and out_len >= 8)
+ * runs a split-K form (fixed 128-channel splits of the x_proj reduction, so
  * every token's bits are independent of the sequence length) that needs `workspace` of
- * vm_conv_proj_workspace_bytes() bytes; larger batches need none (NULL, 0), and address
+ * vm_conv_proj_workspace_bytes() bytes; other shapes need none (NULL, 0), and address
  * x rows, u rows and the conv state through 31-bit buffer offsets: VM_E_INVALID when the xz
  * rows of the sequences one 64-row tile touches span 2 GiB (about 230k tokens at dim 1152)
  * or the conv state does.

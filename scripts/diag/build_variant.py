@@ -129,18 +129,20 @@ VARIANTS = {
     # its own XCD, so the split partials it loads sit in that XCD's L2 (same bits)
     "xr_xcd": [("vm_inproj_conv.hip", "// x_dbl = bf16(sum of the split partials in split order) — xdbl_dt_tm_kernel's sum (from\n// 0, split 0 first, fp32) without its dt phase, one thread per (token, 4 columns) so the\n// whole reduction is one round of loads (that kernel's 64-token tiles take two dependent\n// rounds on a 50-workgroup grid at B = 1).  dt == NULL only (the scan computes dt).\ntemplate <int NSPL>\n__global__ __launch_bounds__(256) void xdbl_reduce_kernel(const InConvParams q) {\n  const ConvProjTmArgs& p = q.a;\n  const int q4 = (p.e + 3) >> 2;\n  const int it = blockIdx.x * 256 + threadIdx.x;\n  if (it >= q.ntok * q4) return;\n  const int t = it / q4, e0 = (it - t * q4) * 4;",
                 "// The token range [lo, hi) of the row tiles whose split 0 ran on XCD x in inproj_conv_kernel\n// (its XCD-contiguous numbering of the x tiles: XCD x took logical tiles [start, start + count))\n__device__ __forceinline__ void ic_xcd_tokens(const InConvParams& q, int x, int& lo, int& hi) {\n  const int nwg = q.nxr * q.nsplit, qq = nwg >> 3, rr = nwg & 7;\n  const int start = x < rr ? x * (qq + 1) : rr * (qq + 1) + (x - rr) * qq;\n  const int end = start + qq + (x < rr ? 1 : 0);\n  const int rt_a = (start + q.nsplit - 1) / q.nsplit, rt_b = (end + q.nsplit - 1) / q.nsplit;\n  lo = min(rt_a * kIcOut, q.ntok);\n  hi = min(rt_b * kIcOut, q.ntok);\n}\n\n// x_dbl = bf16(sum of the split partials in split order) — xdbl_dt_tm_kernel's sum (from\n// 0, split 0 first, fp32) without its dt phase, one thread per (token, 4 columns) so the\n// whole reduction is one round of loads (that kernel's 64-token tiles take two dependent\n// rounds on a 50-workgroup grid at B = 1).  dt == NULL only (the scan computes dt).  Block b\n// runs on XCD b % 8 (round-robin dispatch; placement is a speed choice only) and sums the\n// tokens of the row tiles inproj_conv_kernel ran there, so its partial loads hit that XCD's L2.\ntemplate <int NSPL>\n__global__ __launch_bounds__(256) void xdbl_reduce_kernel(const InConvParams q) {\n  const ConvProjTmArgs& p = q.a;\n  const int q4 = (p.e + 3) >> 2;\n  int lo, hi;\n  ic_xcd_tokens(q, blockIdx.x & 7, lo, hi);\n  const int it = lo * q4 + (blockIdx.x >> 3) * 256 + threadIdx.x;\n  if (it >= hi * q4) return;\n  const int t = it / q4, e0 = (it - t * q4) * 4;"),
-               ("vm_inproj_conv.hip", '    const unsigned blocks = static_cast<unsigned>((ntok * ((e + 3) / 4) + 255) / 256);',
-                "    // 8 x (the most tokens any XCD's row tiles hold) threads, in 256-thread blocks\n    int most = 0;\n    {\n      const int nwg = q.nxr * q.nsplit, qq = nwg >> 3, rr = nwg & 7;\n      for (int x = 0; x < 8; ++x) {\n        const int start = x < rr ? x * (qq + 1) : rr * (qq + 1) + (x - rr) * qq;\n        const int end = start + qq + (x < rr ? 1 : 0);\n        const long long lo = std::min<long long>((start + q.nsplit - 1) / q.nsplit * (long long)kIcOut, ntok);\n        const long long hi = std::min<long long>((end + q.nsplit - 1) / q.nsplit * (long long)kIcOut, ntok);\n        most = std::max(most, static_cast<int>(hi - lo));\n      }\n    }\n    const unsigned blocks = 8u * static_cast<unsigned>((most * ((e + 3) / 4) + 255) / 256);")],
+               ("vm_inproj_conv.hip", "dim3(pl.reduce.gx), dim3(pl.reduce.block), 0, s, q); break;",
+                "dim3(blocks), dim3(pl.reduce.block), 0, s, q); break;"),
+               ("vm_inproj_conv.hip", '  } else {\n    switch (pl.NSPL) {',
+                "  } else {\n    const long long ntok = pl.ntok;\n    // 8 x (the most tokens any XCD's row tiles hold) threads, in 256-thread blocks\n    int most = 0;\n    {\n      const int nwg = q.nxr * q.nsplit, qq = nwg >> 3, rr = nwg & 7;\n      for (int x = 0; x < 8; ++x) {\n        const int start = x < rr ? x * (qq + 1) : rr * (qq + 1) + (x - rr) * qq;\n        const int end = start + qq + (x < rr ? 1 : 0);\n        const long long lo = std::min<long long>((start + q.nsplit - 1) / q.nsplit * (long long)kIcOut, ntok);\n        const long long hi = std::min<long long>((end + q.nsplit - 1) / q.nsplit * (long long)kIcOut, ntok);\n        most = std::max(most, static_cast<int>(hi - lo));\n      }\n    }\n    const unsigned blocks = 8u * static_cast<unsigned>((most * ((e + 3) / 4) + 255) / 256);\n    switch (pl.NSPL) {")],
     # small-batch conv_proj: the two-launch split-K form instead of the fused kernel
-    "cp_splitk": [("vm_conv_proj.hip", "    if (conv_proj_fused_ok(a)) conv_proj_fused_launch(a, st);",
-                   "    if (false) conv_proj_fused_launch(a, st);")],
+    "cp_splitk": [("vm_conv_proj_plan.h", "    if (fused) {\n", "    if (false) {\n")],
     # small-M GEMM with 64-row tiles at every shape
     "lin64": [("vm_gemm.hip", "  const bool big = (long long)((m + 127) / 128) * nt >= 384;",
                "  const bool big = false;")],
     # split-K conv_proj single-tile latency: only token tile 0 (9 workgroups) of each kernel
-    "cx_onetile": [("vm_conv_proj_sk.hip", "  dim3 g1(tiles, q.nsplit);", "  dim3 g1(1, q.nsplit);"),
-                   ("vm_conv_proj_sk.hip", "  const dim3 g2(tiles, cblocks);",
-                    "  const dim3 g2(1, cblocks);")],
+    "cx_onetile": [("vm_conv_proj_sk.hip", "hipStream_t s) {\n  const dim3 g1(pl.main.gx, pl.main.gy);",
+                    "hipStream_t s) {\n  const dim3 g1(1, pl.main.gy);"),
+                   ("vm_conv_proj_sk.hip", "  const dim3 g2(pl.reduce.gx, pl.reduce.gy);",
+                    "  const dim3 g2(1, pl.reduce.gy);")],
     # no conv + SiLU math (u tile = raw x); no x_proj MFMA
     "cx_noconv": [("vm_conv_proj_sk.hip", "      const bool live = step < p.seqlen && tok < q.ntok && cact;",
                    "      const bool live = step < p.seqlen && tok < q.ntok && cact;\n      al = bl; ah = bh;")],
@@ -261,8 +263,8 @@ VARIANTS = {
     "ldma_i128x64": [("vm_gemm.hip", "  if (p.n >= 1024) VM_LDMA_TILE(128, 128, 2, 4)",
                       "  if (p.n >= 1024) VM_LDMA_TILE(128, 64, 3, 2)")],
     # wide conv_proj occupancy probe: LDS padded so 2 (cp_occ2) workgroups fit per CU instead of 3
-    "cp_occ2": [("vm_conv_proj.hip", "  const size_t lds = static_cast<size_t>(dim) * 5 * sizeof(float);",
-                 "  const size_t lds = static_cast<size_t>(dim) * 5 * sizeof(float) + 30000;")],
+    "cp_occ2": [("vm_conv_proj.hip", "dim3(pl.main.block), pl.main.lds, st, p);",
+                 "dim3(pl.main.block), pl.main.lds + 30000, st, p);")],
     # final norm + pooling through the dtype-generic rows kernel only
     "np_generic": [("vm_norm.hip", "constexpr bool kPoolFast = true;", "constexpr bool kPoolFast = false;")],
     "ldma16_i128x128": [("vm_gemm.hip", "  if (p.n >= 1024) VM_LDMA_TILE(128, 128, 2, 4)",
@@ -345,10 +347,10 @@ VARIANTS = {
          "  fu_lds_barrier();\n  VM_STAMP(4)\n  // 16 token rows x dim channels out, 16 B per lane-store"),
         ("vm_conv_proj_sk.hip", "          *reinterpret_cast<const uint4*>(&sDT[t * dtp + qd * 8]);\n  }\n}",
          "          *reinterpret_cast<const uint4*>(&sDT[t * dtp + qd * 8]);\n  }\n  __builtin_amdgcn_s_waitcnt(0);\n  __syncthreads();\n  VM_STAMP(5)\n}"),
-        ("vm_conv_proj_sk.hip", "bool conv_proj_fused_ok(const ConvProjTmArgs& a) {",
+        ("vm_conv_proj_sk.hip", "void conv_proj_fused_launch(const SkTmParams& q, const ConvProjPlan& pl, hipStream_t s) {",
          "}  // namespace vm\nextern \"C\" int vm_dbg_read_stamps(void* dst) {\n"
          "  return static_cast<int>(hipMemcpyFromSymbol(dst, HIP_SYMBOL(vm::vm_dbg_stamps), sizeof(vm::vm_dbg_stamps)));\n}\n"
-         "namespace vm {\nbool conv_proj_fused_ok(const ConvProjTmArgs& a) {"),
+         "namespace vm {\nvoid conv_proj_fused_launch(const SkTmParams& q, const ConvProjPlan& pl, hipStream_t s) {"),
     ],
     # phase timestamps of the one-launch chunked scan (PASS 3) per workgroup: entry (0),
     # start-up loads landed (1), PASS 1 steps done (2), segments composed and aggregate
@@ -419,10 +421,10 @@ VARIANTS = {
          "  VM_STAMP(5)\n  // W_dt fragments for this wave's dt channels (128 per wave"),
         ("vm_conv_proj_sk.hip", "  fu_lds_barrier();  // every wave's u tile is consumed: the area becomes the partials",
          "  VM_STAMP(6)\n  fu_lds_barrier();  // every wave's u tile is consumed: the area becomes the partials\n  VM_STAMP(7)"),
-        ("vm_conv_proj_sk.hip", "bool conv_proj_fused_ok(const ConvProjTmArgs& a) {",
+        ("vm_conv_proj_sk.hip", "void conv_proj_fused_launch(const SkTmParams& q, const ConvProjPlan& pl, hipStream_t s) {",
          "}  // namespace vm\nextern \"C\" int vm_dbg_read_stamps(void* dst) {\n"
          "  return static_cast<int>(hipMemcpyFromSymbol(dst, HIP_SYMBOL(vm::vm_dbg_stamps), sizeof(vm::vm_dbg_stamps)));\n}\n"
-         "namespace vm {\nbool conv_proj_fused_ok(const ConvProjTmArgs& a) {"),
+         "namespace vm {\nvoid conv_proj_fused_launch(const SkTmParams& q, const ConvProjPlan& pl, hipStream_t s) {"),
     ],
     # timing probe: every step reads the segment's first B/C row (L1/K$-resident), so the
     # chunk kernel's time without the per-step scalar-load latency shows (results wrong)

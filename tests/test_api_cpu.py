@@ -467,6 +467,210 @@ def test_conv_proj_wide_offset_limit_is_rejected_on_the_host():
     assert call(300_000, 0) == 0  # empty batch: nothing to launch, nothing to check
 
 
+def _conv_proj_query_rows():
+    table = json.load(open(os.path.join(ROOT, "tests", "golden", "conv_proj_queries.json")))
+    assert table["columns"] == [
+        "batch", "out_len", "seqlen", "dim", "e", "e_pad", "r_pad", "k", "cs_dtype",
+        "dt_softplus", "has_dt", "width", "fits", "workspace_bytes", "in_proj_fits",
+        "in_proj_workspace_bytes", "cm_workspace_bytes"]
+    return table["rows"]
+
+
+def test_conv_proj_queries_reproduce_the_recorded_table():
+    """The five host queries of the mixer middle against tests/golden/conv_proj_queries.json:
+    their answers as recorded from the library built at the commit the file names (before
+    the host side was folded into vm_conv_proj_plan.h::plan_conv_proj), over shapes on both
+    sides of every form limit.  The strides are the mixer's (see gen_conv_proj_queries.py).
+    Every row must come back unchanged."""
+    lib = _lib.load()
+    rows = _conv_proj_query_rows()
+    assert len(rows) >= 300
+    bad = []
+    for row in rows:
+        b, lp, l, d, e, ep, rp, k, cs, spd, has_dt, w = row[:12]
+        got = [lib.vm_conv_proj_fits(b, lp, l, d, e, rp, spd, lp * 2 * d, 2 * d, int(cs >= 0),
+                                     max(cs, 0), d * w, w, w, d),
+               lib.vm_conv_proj_workspace_bytes(b, lp, d, e),
+               lib.vm_in_proj_conv_proj_fits(k, b, lp, d, e, ep, rp, w, has_dt),
+               lib.vm_in_proj_conv_proj_workspace_bytes(b, lp, d, e),
+               lib.vm_conv_proj_cm_workspace_bytes(b, lp, d, e)]
+        if got != row[12:]:
+            bad.append((row[:12], row[12:], got))
+    assert not bad, bad[:5]
+
+
+def test_conv_proj_plan_check_program_passes_under_sanitizers(tmp_path):
+    """tests/host/conv_proj_plan_check.cpp walks vm_conv_proj_plan.h::plan_conv_proj over
+    shapes x options x the three entries and exits non-zero on any plan whose form differs
+    from the rules written out there, whose template selectors are not instantiated, whose
+    tiles do not cover the tokens, whose workspace is below what its kernels index, whose
+    buffer-resource extents reach 2^31 bytes or whose LDS does not fit.  Built as a program
+    of its own under ASan + UBSan, as scan_plan_check.cpp is."""
+    rocm_clang = "/opt/rocm/llvm/bin/clang++"
+    cxx = [rocm_clang] if os.path.exists(rocm_clang) else \
+        [shutil.which("g++") or "g++", "-static-libasan", "-static-libubsan"]
+    exe = str(tmp_path / "conv_proj_plan_check")
+    subprocess.run(cxx + ["-std=c++17", "-O1", "-g", "-fsanitize=address,undefined",
+                    "-fno-sanitize-recover=all", "-I", os.path.join(ROOT, "videomamba_amd", "csrc"),
+                    os.path.join(ROOT, "tests", "host", "conv_proj_plan_check.cpp"), "-o", exe],
+                   check=True, timeout=120)
+    run = subprocess.run([exe], capture_output=True, text=True, timeout=120)
+    assert run.returncode == 0, run.stdout + run.stderr
+    assert " 0 failures" in run.stdout
+
+
+def test_conv_proj_small_max_batch_matches_the_library():
+    """kernels.CONV_PROJ_SMALL_MAX_BATCH is the library's kSkMaxBatch: the workspace query
+    answers up to that batch and reports 0 one above."""
+    from videomamba_amd import kernels as K
+    lib = _lib.load()
+    B = K.CONV_PROJ_SMALL_MAX_BATCH
+    assert lib.vm_conv_proj_workspace_bytes(B, 3144, 1152, 68) > 0
+    assert lib.vm_conv_proj_workspace_bytes(B + 1, 3144, 1152, 68) == 0
+
+
+def _fake(i, off=0):
+    return ctypes.c_void_p(((i + 1) << 20) + off)  # 16-byte aligned (off 0), never dereferenced
+
+
+def _conv_proj_tm_call(lib, **over):
+    """vm_conv_proj_fwd on fake pointers at the mixer's M geometry; `over` replaces
+    arguments by name."""
+    a = dict(D=1152, E=68, Ep=80, R=36, Rp=64, L=3137, Lp=3144, batch=2, width=4,
+             dtype=_lib.VM_DTYPE_BF16, spd=0, xz=_fake(0), cw=_fake(1), cs_in=None, cs_out=None,
+             wx=_fake(3), wdt=_fake(4), u=_fake(5), xdbl=_fake(6), dt=_fake(7), ws=_fake(8),
+             ws_bytes=1 << 40, u_sb=None)
+    a.update(over)
+    s = SimpleNamespace(**a)
+    u_sb = s.Lp * s.D if s.u_sb is None else s.u_sb
+    return lib.vm_conv_proj_fwd(
+        s.xz, s.Lp * 2 * s.D, 2 * s.D, s.cw, _fake(2),
+        s.cs_in, 0, s.D * 4, 4, s.cs_out, 0, s.D * 4, 4,
+        s.wx, s.E, s.Ep, s.wdt, s.R, s.Rp,
+        s.u, u_sb, s.D, s.xdbl, s.Lp * s.E, s.E, s.dt, s.Lp * s.D, s.D,
+        None, s.spd, s.Lp, s.batch, s.D, s.L, s.width, s.dtype, s.ws, s.ws_bytes, None)
+
+
+def _in_proj_conv_proj_call(lib, **over):
+    a = dict(D=1152, K=576, E=68, Ep=80, R=36, Rp=64, L=3137, Lp=3144, batch=2, width=4,
+             hn=_fake(0), w_in=_fake(1), z=_fake(2), cw=_fake(3), cs_in=None, cs_out=None,
+             wx=_fake(5), wdt=_fake(6), u=_fake(7), xdbl=_fake(8), dt=_fake(9), ws=_fake(10),
+             ws_bytes=1 << 40, ldh=None)
+    a.update(over)
+    s = SimpleNamespace(**a)
+    return lib.vm_in_proj_conv_proj_fwd(
+        s.hn, s.K if s.ldh is None else s.ldh, s.w_in, s.K, s.K, s.z, s.D, s.cw, _fake(4),
+        s.cs_in, 0, s.D * 4, 4, s.cs_out, 0, s.D * 4, 4,
+        s.wx, s.E, s.Ep, s.wdt, s.R, s.Rp,
+        s.u, s.D, s.xdbl, s.E, s.dt, s.D,
+        s.Lp, s.batch, s.D, s.L, s.width, s.ws, s.ws_bytes, None)
+
+
+def _conv_proj_cm_call(lib, **over):
+    a = dict(D=1152, E=68, Ep=80, R=36, Rp=64, L=3137, Lp=3144, batch=2, width=4,
+             xz=_fake(0), cw=_fake(1), cs_in=None, cs_out=None, wx=_fake(3), wdt=_fake(4),
+             u=_fake(5), xdbl=_fake(6), dt=_fake(7), ws=_fake(8), ws_bytes=1 << 40, x_sd=None)
+    a.update(over)
+    s = SimpleNamespace(**a)
+    ntok = s.batch * s.Lp
+    return lib.vm_conv_proj_cm_fwd(
+        s.xz, ntok if s.x_sd is None else s.x_sd, s.cw, _fake(2),
+        s.cs_in, 0, s.D * 4, 4, s.cs_out, 0, s.D * 4, 4,
+        s.wx, s.E, s.Ep, s.wdt, s.R, s.Rp,
+        s.u, ntok, s.xdbl, ntok, s.dt, ntok,
+        s.Lp, s.batch, s.D, s.L, s.width, s.ws, s.ws_bytes, None)
+
+
+# 9 splits x (2 x 3144) tokens x 68 floats: the token-major partials of the calls above;
+# the channel-major layout [split][e][tok] has the same size at E % 4 == 0
+_SK_NEED = 9 * 2 * 3144 * 68 * 4
+
+# (entry, replaced arguments, return code, distinguishing part of vm_last_error()), every
+# row as the library at 194923f (before vm_conv_proj_plan.h) answered it.  Refused calls and
+# empty batches only: an accepted call would launch on the fake pointers.
+_CONV_PROJ_REFUSALS = [
+    # null pointer
+    (_conv_proj_tm_call, dict(xz=None), -1, b"vm_conv_proj_fwd: null required pointer"),
+    (_conv_proj_tm_call, dict(wdt=None), -1, b"vm_conv_proj_fwd: null required pointer"),
+    (_in_proj_conv_proj_call, dict(hn=None), -1, b"vm_in_proj_conv_proj_fwd: null required pointer"),
+    (_in_proj_conv_proj_call, dict(z=None), -1, b"vm_in_proj_conv_proj_fwd: null required pointer"),
+    (_conv_proj_cm_call, dict(dt=None), -1, b"vm_conv_proj_cm_fwd: null required pointer"),
+    # shape
+    (_conv_proj_tm_call, dict(D=1100), -1, b"vm_conv_proj_fwd: unsupported shape (bf16, dim % 64"),
+    (_conv_proj_tm_call, dict(Ep=144, E=130), -1, b"vm_conv_proj_fwd: unsupported shape"),
+    (_conv_proj_tm_call, dict(Rp=96), -1, b"vm_conv_proj_fwd: unsupported shape"),
+    (_conv_proj_tm_call, dict(dtype=_lib.VM_DTYPE_F32), -1, b"vm_conv_proj_fwd: unsupported shape"),
+    (_in_proj_conv_proj_call, dict(K=1024), -1,
+     b"vm_in_proj_conv_proj_fwd: unsupported shape (bf16; k in {192 .. 1536} by 64-steps; "
+     b"batch <= 8, out_len >= 56 and even, dim % 128 == 0 and <= 2048, R + 2N <= 76, "
+     b"e_pad <= 80"),
+    (_in_proj_conv_proj_call, dict(batch=9), -1, b"vm_in_proj_conv_proj_fwd: unsupported shape"),
+    (_in_proj_conv_proj_call, dict(batch=0), -1, b"vm_in_proj_conv_proj_fwd: unsupported shape"),
+    (_in_proj_conv_proj_call, dict(Lp=54, L=50), -1, b"vm_in_proj_conv_proj_fwd: unsupported shape"),
+    (_in_proj_conv_proj_call, dict(D=2176), -1, b"vm_in_proj_conv_proj_fwd: unsupported shape"),
+    (_in_proj_conv_proj_call, dict(D=1088), -1, b"vm_in_proj_conv_proj_fwd: unsupported shape"),
+    (_in_proj_conv_proj_call, dict(E=78), -1, b"vm_in_proj_conv_proj_fwd: unsupported shape"),
+    (_in_proj_conv_proj_call, dict(Ep=96), -1, b"vm_in_proj_conv_proj_fwd: unsupported shape"),
+    (_in_proj_conv_proj_call, dict(Rp=96), -1, b"vm_in_proj_conv_proj_fwd: unsupported shape"),
+    (_conv_proj_cm_call, dict(Lp=3140), -1, b"vm_conv_proj_cm_fwd: unsupported shape (dim % 64"),
+    (_conv_proj_cm_call, dict(D=1100), -1, b"vm_conv_proj_cm_fwd: unsupported shape"),
+    # alignment
+    (_conv_proj_tm_call, dict(xz=_fake(0, 2)), -1, b"vm_conv_proj_fwd: xz / u / dt / weights need 16-byte"),
+    (_conv_proj_tm_call, dict(Lp=3145), -1, b"vm_conv_proj_fwd: xz / u / dt / weights need 16-byte"),
+    (_conv_proj_tm_call, dict(D=8256), -1, b"x_dbl 4-byte aligned, even out_len and e, dim <= 8192"),
+    (_in_proj_conv_proj_call, dict(hn=_fake(0, 2)), -1, b"16-byte aligned rows; hn under 2 GB"),
+    (_in_proj_conv_proj_call, dict(ldh=580), -1, b"vm_in_proj_conv_proj_fwd: unsupported shape"),
+    (_conv_proj_cm_call, dict(u=_fake(5, 8)), -1,
+     b"vm_conv_proj_cm_fwd: x / u / dt rows and the weights must be 16-byte aligned"),
+    (_conv_proj_cm_call, dict(x_sd=2 * 3144 + 4), -1, b"must be 16-byte aligned"),
+    # batch-contiguity (token-major outputs)
+    (_conv_proj_tm_call, dict(u_sb=3144 * 1152 + 8), -1,
+     b"vm_conv_proj_fwd: u / x_dbl / dt must be batch-contiguous (sb == out_len * sl)"),
+    # aliasing
+    (_conv_proj_tm_call, dict(cs_in=_fake(9), cs_out=_fake(9)), -1,
+     b"vm_conv_proj_fwd: conv_state_out must not alias conv_state_in"),
+    (_in_proj_conv_proj_call, dict(cs_in=_fake(11), cs_out=_fake(11)), -1,
+     b"vm_in_proj_conv_proj_fwd: conv_state_out must not alias conv_state_in"),
+    (_conv_proj_cm_call, dict(cs_in=_fake(9), cs_out=_fake(9)), -1,
+     b"vm_conv_proj_cm_fwd: conv_state_out must not alias conv_state_in"),
+    # missing or short workspace
+    (_conv_proj_tm_call, dict(ws=None), -1,
+     b"vm_conv_proj_fwd: batch <= 8 needs a workspace of %d bytes (vm_conv_proj_workspace_bytes)" % _SK_NEED),
+    (_conv_proj_tm_call, dict(ws_bytes=_SK_NEED - 1), -1, b"needs a workspace of %d bytes" % _SK_NEED),
+    # the fused form writes no partials, yet the entry asks for them at every small batch
+    (_conv_proj_tm_call, dict(ws_bytes=0, batch=1), -1, b"needs a workspace of %d bytes" % (_SK_NEED // 2)),
+    (_in_proj_conv_proj_call, dict(ws=None), -1,
+     b"vm_in_proj_conv_proj_fwd: needs a workspace of %d bytes "
+     b"(vm_in_proj_conv_proj_workspace_bytes)" % _SK_NEED),
+    (_in_proj_conv_proj_call, dict(ws_bytes=_SK_NEED - 1), -1, b"needs a workspace of %d bytes" % _SK_NEED),
+    (_conv_proj_cm_call, dict(ws=None), -1,
+     b"vm_conv_proj_cm_fwd: workspace of %d bytes required" % _SK_NEED),
+    (_conv_proj_cm_call, dict(ws_bytes=_SK_NEED - 1), -1, b"workspace of %d bytes required" % _SK_NEED),
+    # 31-bit offsets
+    (_conv_proj_tm_call, dict(batch=9, L=300_000, Lp=300_000), -1,
+     b"vm_conv_proj_fwd: batch > 8 needs a sequence of xz under 1 GiB (31-bit buffer offsets)"),
+    (_conv_proj_tm_call, dict(batch=2, spd=1, L=300_000, Lp=300_000), -1, b"31-bit buffer offsets"),
+    (_in_proj_conv_proj_call, dict(batch=8, L=300_000, Lp=300_000), -1, b"hn under 2 GB"),
+    # empty batch: nothing to launch (the in_proj entry refuses it, above)
+    (_conv_proj_tm_call, dict(batch=0), 0, None),
+    (_conv_proj_tm_call, dict(batch=0, ws=None), 0, None),
+    (_conv_proj_cm_call, dict(batch=0), 0, None),
+    (_conv_proj_cm_call, dict(batch=0, ws=None), 0, None),
+]
+
+
+@pytest.mark.parametrize("row", range(len(_CONV_PROJ_REFUSALS)))
+def test_conv_proj_entries_refuse_as_recorded(row):
+    """The three mixer-middle entries refuse on the host, before any HIP call, with the
+    return code and message they had before the plan (fake pointers, never dereferenced):
+    null pointer, shape, alignment, batch-contiguity, aliasing, workspace, 31-bit offsets."""
+    call, over, rc, text = _CONV_PROJ_REFUSALS[row]
+    lib = _lib.load()
+    assert call(lib, **over) == rc
+    if text is not None:
+        assert text in lib.vm_last_error(), lib.vm_last_error()
+
+
 def test_conv_proj_fits_query_routes_long_sequences_to_the_unfused_path():
     """the wide conv_proj form's 31-bit offsets reject ~230k-token sequences at
     batch > 8; vm_conv_proj_fits reports that on the host and the mixer's fused-path test

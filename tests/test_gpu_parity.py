@@ -926,6 +926,63 @@ def test_conv_proj_split_k_matches_wide_kernel(d_model):
     _close(u1[:L].t().unsqueeze(0), ref_u, 1e-2)
 
 
+def test_conv_proj_split_k_ten_splits_matches_wide_kernel():
+    """The plan hands the split-K form's reduce kernel its split count as a template
+    selector (NSPL); d_model 640 -> D = 1280 is 10 splits, one more than any other test runs
+    (and past the fused form's 9), with R = 40 and E = 72.  L = 37 in rows of 40 with a
+    carried bf16 conv state: 2 clips (split-K) against the same clips among 9 (wide), u
+    bit-identical, x_dbl within one bf16 rounding, and each form's x_dbl / dt against the
+    fp32 projections of its own u / x_dbl, as test_conv_proj_split_k_matches_wide_kernel."""
+    from videomamba_amd.mamba_simple import Mamba
+    torch.manual_seed(640)
+    m = Mamba(d_model=640, d_state=16, d_conv=4, expand=2, layer_idx=0).to(DEV, torch.bfloat16)
+    Dm, E, R, W = m.d_inner, m.dt_rank + 2 * m.d_state, m.dt_rank, m.d_conv
+    assert (Dm, R, E) == (1280, 40, 72)
+    _, _, _, cw, cb = m._fp32_params()
+    wx_pad, wdt_pad = m._padded_proj_weights()
+    st = torch.cuda.current_stream().cuda_stream
+    L, Lp = 37, 40
+    xz9 = torch.randn(9, Lp, 2 * Dm, device=DEV).to(torch.bfloat16)
+    xz9[:, L:] = 0
+    cs9 = torch.randn(9, Dm, W, device=DEV).to(torch.bfloat16)
+    outs = []
+    for bsz in (2, 9):
+        n = bsz * Lp
+        xz = xz9[:bsz].reshape(n, 2 * Dm).contiguous()
+        cs = cs9[:bsz].contiguous()
+        u = torch.empty(n, Dm, device=DEV, dtype=torch.bfloat16)
+        xd = torch.empty(n, E, device=DEV, dtype=torch.bfloat16)
+        dt = torch.empty(n, Dm, device=DEV, dtype=torch.bfloat16)
+        K.conv_proj_raw(xz, (Lp * 2 * Dm, 2 * Dm), cw, cb, cs, (Dm * W, W), None, (0, 0),
+                        wx_pad, E, wdt_pad, R, u, (Lp * Dm, Dm), xd, (Lp * E, E), dt,
+                        (Lp * Dm, Dm), Lp, bsz, Dm, L, W, st)
+        outs.append((u[:2 * Lp], xd[:2 * Lp], dt[:2 * Lp]))
+    torch.cuda.synchronize()
+    (u2, xd2, dt2), (u9, xd9, dt9) = outs
+    assert torch.equal(u2, u9)
+    pad = torch.arange(2 * Lp, device=DEV) % Lp >= L
+    assert u2[~pad].float().abs().any()
+    assert not u2[pad].float().abs().any() and not dt2[pad].float().abs().any()
+    ulp = lambda t: t.float().abs() * 2.0 ** -7 + 1e-6  # noqa: E731
+    assert ((xd9.float() - xd2.float()).abs() <= ulp(xd2)).all()
+    for u, xd, dt in outs:
+        want_xd = F.linear(u.float(), m.x_proj.weight.float())
+        assert ((xd.float() - want_xd).abs() <= want_xd.abs() * 2.0 ** -7 + 1e-3).all()
+        want_dt = F.linear(xd[:, :R].float(), m.dt_proj.weight.float())
+        assert ((dt.float() - want_dt).abs() <= want_dt.abs() * 2.0 ** -7 + 1e-3).all()
+    # dt across the forms: what the x_dbl[:, :R] differences can move the fp32 sum, its
+    # accumulation error (64 terms, 2^-24 each, on the sum of magnitudes), and each side's
+    # rounding to bf16 (half an ulp: 2^-8 relative)
+    wdt_abs = m.dt_proj.weight.float().abs()
+    moved = F.linear((xd9[:, :R].float() - xd2[:, :R].float()).abs(), wdt_abs)
+    acc = 2 * 64 * 2.0 ** -24 * F.linear(xd2[:, :R].float().abs(), wdt_abs)
+    rnd = (dt2.float().abs() + dt9.float().abs()) * 2.0 ** -8 * (1 + 2.0 ** -8)
+    assert ((dt9.float() - dt2.float()).abs() <= moved + acc + rnd + 1e-30).all()
+    ref_u, _ = orc.causal_conv1d(xz9[:1, :L, :Dm].transpose(1, 2).cpu(), cw.cpu(), cb.cpu(), True,
+                                 cs9[:1].cpu())
+    _close(u2[:L].t().unsqueeze(0), ref_u, 1e-2)
+
+
 @pytest.mark.parametrize("d_model", [576, 96])
 def test_conv_proj_fused_small_batch_matches_split_k_bitwise(d_model):
     """Small batches run conv + x_proj + dt_proj as one fused launch when out_len >= 24

@@ -47,7 +47,6 @@ struct ConvProjParams {
   int batch, dim, seqlen, lp, rows, e, e_pad, r, r_pad, width, csi_dtype, cso_dtype;
 };
 
-constexpr int kCPTok = 64;   // token rows per workgroup
 constexpr int kCPCh = 64;    // channels per chunk
 constexpr int kCPPad = 72;   // LDS row pitch (bf16): 144 B rows keep b128 reads conflict-light
 constexpr int kCPMaxNB = 8;  // (R + 2N) <= 128
@@ -452,43 +451,23 @@ __global__ __launch_bounds__(256) void conv_state_out_kernel(const ConvProjParam
 using namespace vm;
 
 extern "C" long long vm_conv_proj_workspace_bytes(int batch, int out_len, int dim, int e) {
-  if (batch > kSkMaxBatch) return 0;
-  return conv_proj_sk_workspace_bytes(batch, out_len, dim, e);
-}
-
-// Which form vm_conv_proj_fwd runs (the split-K / fused small-batch form for batch <=
-// kSkMaxBatch, else the wide kernel), and whether the wide kernel's 31-bit buffer offsets
-// cover the operands: the x rows of the sequences one workgroup's 64 rows touch, the conv
-// state, the u rows.  Shared by the launcher and the host query vm_conv_proj_fits.
-static bool conv_proj_small_form(int batch, int dim, int e, int r_pad, int spd, int out_len) {
-  return batch <= kSkMaxBatch && !spd && dim <= 2048 && (e + 3) / 4 * 4 <= kSkMaxEp &&
-         r_pad <= 80 && out_len >= 8;
-}
-static bool conv_proj_wide_offsets_ok(int batch, int out_len, int seqlen, int dim,
-                                      long long xz_sb, long long xz_sl, bool has_cs_in,
-                                      int cs_in_dtype, long long csi_sb, long long csi_sd,
-                                      int width, long long u_sl) {
-  constexpr long long kOff31 = 0x7fffff00LL;
-  const int cs_es = has_cs_in && cs_in_dtype == VM_DTYPE_BF16 ? 2 : 4;
-  return ((long long)(kCPTok / out_len + 1) * xz_sb + (long long)seqlen * xz_sl + dim) * 2 <=
-             kOff31 &&
-         (!has_cs_in ||
-          ((long long)(batch - 1) * csi_sb + (long long)(dim - 1) * csi_sd + width) * cs_es <=
-              kOff31) &&
-         (long long)kCPTok * u_sl * 2 <= kOff31;
+  ConvProjPlanIn in{};
+  in.batch = batch; in.out_len = out_len; in.dim = dim; in.e = e;
+  return plan_conv_proj(in).ws_query;
 }
 
 extern "C" int vm_conv_proj_fits(int batch, int out_len, int seqlen, int dim, int e, int r_pad,
                                  int dt_softplus, long long xz_sb, long long xz_sl,
                                  int has_conv_state_in, int cs_in_dtype, long long csi_sb,
                                  long long csi_sd, int width, long long u_sl) {
-  if (batch <= 0 || out_len <= 0) return 1;
-  if (conv_proj_small_form(batch, dim, e, r_pad, dt_softplus != 0, out_len)) return 1;
-  return conv_proj_wide_offsets_ok(batch, out_len, seqlen, dim, xz_sb, xz_sl,
-                                   has_conv_state_in != 0, cs_in_dtype, csi_sb, csi_sd, width,
-                                   u_sl)
-             ? 1
-             : 0;
+  ConvProjPlanIn in{};
+  in.batch = batch; in.out_len = out_len; in.seqlen = seqlen; in.dim = dim; in.e = e;
+  in.r_pad = r_pad; in.width = width; in.dt_softplus = dt_softplus != 0;
+  in.xz_sb = xz_sb; in.xz_sl = xz_sl; in.u_sl = u_sl;
+  in.has_cs_in = has_conv_state_in != 0; in.cs_in_bf16 = cs_in_dtype == VM_DTYPE_BF16;
+  in.csi_sb = csi_sb; in.csi_sd = csi_sd;
+  const ConvProjPlan pl = plan_conv_proj(in);
+  return pl.form != ConvProjForm::kNone || pl.why == ConvProjWhy::kEmpty ? 1 : 0;
 }
 
 extern "C" int vm_conv_proj_fwd(const void* xz, long long xz_sb, long long xz_sl,
@@ -502,10 +481,9 @@ extern "C" int vm_conv_proj_fwd(const void* xz, long long xz_sb, long long xz_sl
                                 void* dt, long long dt_sb, long long dt_sl,
                                 const float* dt_bias, int dt_softplus, int out_len, int batch, int dim, int seqlen, int width, int dtype,
                                 void* workspace, long long workspace_bytes, vm_stream_t stream) {
-  if (!xz || !conv_weight || !wx_pad || !u || !xdbl || (dt && !wdt_pad)) {
-    vmhost::set_error("vm_conv_proj_fwd: null required pointer");
-    return VM_E_INVALID;
-  }
+  static const char* const kEntry = "vm_conv_proj_fwd";
+  if (!xz || !conv_weight || !wx_pad || !u || !xdbl || (dt && !wdt_pad))
+    return conv_proj_refuse(kEntry, kConvProjNull);
   if (dtype != VM_DTYPE_BF16 || batch < 0 || dim <= 0 || dim % kCPCh != 0 || seqlen < 1 ||
       out_len < seqlen || width < 1 || width > 4 || e < 1 || e_pad % 16 != 0 || e_pad < e ||
       e_pad > kCPMaxNB * 16 || r < 1 || r > e || (dt && ((r_pad != 32 && r_pad != 64) || r_pad < r)) ||
@@ -527,73 +505,68 @@ extern "C" int vm_conv_proj_fwd(const void* xz, long long xz_sb, long long xz_sl
                       "(sb == out_len * sl)");
     return VM_E_INVALID;
   }
-  if (cs_out && cs_in == cs_out) {
-    vmhost::set_error("vm_conv_proj_fwd: conv_state_out must not alias conv_state_in");
+  if (cs_out && cs_in == cs_out) return conv_proj_refuse(kEntry, kConvProjAlias);
+  if (batch == 0) return VM_OK;
+  // dt_proj runs inside conv_proj; dt == nullptr skips it (conv + x_proj only: a consumer
+  // that projects dt itself)
+  const ConvProjTmArgs a = conv_proj_tm_args(
+      xz, xz_sl, conv_weight, conv_bias, cs_in, cs_in_dtype, csi_sb, csi_sd, cs_out,
+      cs_out_dtype, cso_sb, cso_sd, wx_pad, e, e_pad, wdt_pad, r, r_pad, u, u_sl, xdbl, xd_sl,
+      dt, dt_sl, out_len, batch, dim, seqlen, width);
+  ConvProjPlanIn in = conv_proj_plan_in(a, ConvProjEntry::kConvProj);
+  in.xz_sb = xz_sb;
+  in.dt_softplus = dt_softplus != 0;
+  const ConvProjPlan pl = plan_conv_proj(in);
+  hipStream_t st = static_cast<hipStream_t>(stream);
+  if (pl.why == ConvProjWhy::kWideOffsets) {
+    vmhost::set_error("vm_conv_proj_fwd: batch > %d needs a sequence of xz under 1 GiB "
+                      "(31-bit buffer offsets)", kSkMaxBatch);
     return VM_E_INVALID;
   }
-  if (batch == 0) return VM_OK;
+  if (pl.small()) {
+    // small batch: the split-K form (vm_conv_proj_sk.hip) fills the chip and keeps the
+    // x_proj reduction order fixed per token
+    if (!workspace || workspace_bytes < pl.ws_need) {
+      vmhost::set_error("vm_conv_proj_fwd: batch <= %d needs a workspace of %lld bytes "
+                        "(vm_conv_proj_workspace_bytes)", kSkMaxBatch, pl.ws_need);
+      return VM_E_INVALID;
+    }
+    // one fused launch where it applies (bit-identical), else the two split-K launches;
+    // both write the conv state
+    if (pl.form == ConvProjForm::kFused)
+      conv_proj_fused_launch(sk_tm_params(a, pl, nullptr), pl, st);
+    else
+      conv_proj_sk_launch(sk_tm_params(a, pl, static_cast<float*>(workspace)), pl, st);
+    return vmhost::launch_status(kEntry);
+  }
   ConvProjParams p{};
-  p.xz = static_cast<const bf16_t*>(xz); p.cw = conv_weight; p.cb = conv_bias;
+  p.xz = a.x; p.cw = conv_weight; p.cb = conv_bias;
   p.csi = cs_in; p.cso = cs_out;
-  p.wx = static_cast<const bf16_t*>(wx_pad); p.wdt = static_cast<const bf16_t*>(wdt_pad);
-  p.u = static_cast<bf16_t*>(u); p.xdbl = static_cast<bf16_t*>(xdbl);
-  p.dt = static_cast<bf16_t*>(dt);
+  p.wx = a.wx; p.wdt = static_cast<const bf16_t*>(wdt_pad);
+  p.u = a.u; p.xdbl = a.xdbl; p.dt = a.dt;
   p.dtb = dt_bias;
   p.xz_sb = xz_sb; p.xz_sl = xz_sl; p.csi_sb = csi_sb; p.csi_sd = csi_sd;
   p.cso_sb = cso_sb; p.cso_sd = cso_sd;
   p.u_sb = u_sb; p.u_sl = u_sl; p.xd_sb = xd_sb; p.xd_sl = xd_sl; p.dt_sb = dt_sb; p.dt_sl = dt_sl;
   p.batch = batch; p.dim = dim; p.seqlen = seqlen; p.lp = out_len;
-  p.rows = batch * out_len; p.e = e; p.e_pad = e_pad; p.r = r; p.r_pad = r_pad;
+  p.rows = pl.ntok; p.e = e; p.e_pad = e_pad; p.r = r; p.r_pad = r_pad;
   p.width = width; p.csi_dtype = cs_in_dtype; p.cso_dtype = cs_out_dtype;
-  dim3 grid((p.rows + kCPTok - 1) / kCPTok);
-  const size_t lds = static_cast<size_t>(dim) * 5 * sizeof(float);
-  hipStream_t st = static_cast<hipStream_t>(stream);
-  // dt_proj runs inside conv_proj (half-tile dt phase, same LDS budget); dt == nullptr
-  // skips it (conv + x_proj only: a consumer that projects dt itself)
-  const bool fused_dt = dt != nullptr;
-  const bool spd = dt_softplus != 0;
-  if (conv_proj_small_form(batch, dim, e, r_pad, spd, out_len)) {
-    // small batch: the split-K form (vm_conv_proj_sk.hip) fills the chip and keeps the
-    // x_proj reduction order fixed per token
-    const long long need = conv_proj_sk_workspace_bytes(batch, out_len, dim, e);
-    if (!workspace || workspace_bytes < need) {
-      vmhost::set_error("vm_conv_proj_fwd: batch <= %d needs a workspace of %lld bytes "
-                        "(vm_conv_proj_workspace_bytes)", kSkMaxBatch, need);
-      return VM_E_INVALID;
-    }
-    ConvProjTmArgs a{};
-    a.x = p.xz; a.x_tl = xz_sl; a.cw = conv_weight; a.cb = conv_bias;
-    a.csi = cs_in; a.csi_dtype = cs_in_dtype; a.csi_sb = csi_sb; a.csi_sd = csi_sd;
-    a.cso = cs_out; a.cso_dtype = cs_out_dtype; a.cso_sb = cso_sb; a.cso_sd = cso_sd;
-    a.wx = p.wx; a.e = e; a.e_pad = e_pad; a.wdt = fused_dt ? p.wdt : nullptr; a.r = r;
-    a.r_pad = r_pad; a.u = p.u; a.u_tl = u_sl; a.xdbl = p.xdbl; a.xd_tl = xd_sl; a.dt = p.dt;
-    a.dt_tl = dt_sl; a.out_len = out_len; a.batch = batch; a.dim = dim; a.seqlen = seqlen;
-    a.width = width;
-    // one fused launch where it applies (bit-identical), else the two split-K launches;
-    // both write the conv state
-    if (conv_proj_fused_ok(a)) conv_proj_fused_launch(a, st);
-    else conv_proj_sk_launch(a, static_cast<float*>(workspace), st);
-    return vmhost::launch_status("vm_conv_proj_fwd");
-  }
-  if (!conv_proj_wide_offsets_ok(batch, out_len, seqlen, dim, xz_sb, xz_sl, cs_in != nullptr,
-                                 cs_in_dtype, csi_sb, csi_sd, width, u_sl)) {
-    vmhost::set_error("vm_conv_proj_fwd: batch > %d needs a sequence of xz under 1 GiB "
-                      "(31-bit buffer offsets)", kSkMaxBatch);
-    return VM_E_INVALID;
-  }
-  auto go = [&](auto kern) { hipLaunchKernelGGL(kern, grid, dim3(256), lds, st, p); };
-  switch (e_pad / 16) {  // x_proj output blocks
-#define VM_CP_CASE(NBV)                                              \
-    case NBV:                                                        \
-      if (fused_dt && spd) go(conv_proj_kernel<true, NBV, 0, true>); \
-      else if (fused_dt) go(conv_proj_kernel<true, NBV>);            \
-      else go(conv_proj_kernel<false, NBV>);                         \
+  auto go = [&](auto kern) {
+    hipLaunchKernelGGL(kern, dim3(pl.main.gx), dim3(pl.main.block), pl.main.lds, st, p);
+  };
+  switch (pl.NB) {  // x_proj output blocks
+#define VM_CP_CASE(NBV)                                                      \
+    case NBV:                                                                \
+      if (in.want_dt && in.dt_softplus) go(conv_proj_kernel<true, NBV, 0, true>); \
+      else if (in.want_dt) go(conv_proj_kernel<true, NBV>);                  \
+      else go(conv_proj_kernel<false, NBV>);                                 \
       break;
     VM_CP_CASE(1) VM_CP_CASE(2) VM_CP_CASE(3) VM_CP_CASE(4)
     VM_CP_CASE(5) VM_CP_CASE(6) VM_CP_CASE(7) VM_CP_CASE(8)
 #undef VM_CP_CASE
   }
-  if (cs_out)
-    hipLaunchKernelGGL(conv_state_out_kernel, dim3((dim + 255) / 256, batch), dim3(256), 0, st, p);
-  return vmhost::launch_status("vm_conv_proj_fwd");
+  if (pl.state.gx)
+    hipLaunchKernelGGL(conv_state_out_kernel, dim3(pl.state.gx, pl.state.gy), dim3(pl.state.block),
+                       0, st, p);
+  return vmhost::launch_status(kEntry);
 }

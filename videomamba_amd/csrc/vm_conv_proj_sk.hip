@@ -49,9 +49,7 @@ struct ConvProjCmParams {
   int nsplit, split_ch;  // channel splits of the x_proj reduction, channels per split
 };
 
-constexpr int kCmTok = 64;    // token columns per workgroup
-constexpr int kCmPitch = 72;  // LDS row pitch in bf16 (144 B): 16-B aligned rows
-constexpr int kCmHalo = 8;    // tokens staged before the tile (>= width - 1, 16-B aligned)
+// (tile sizes, pitches and LDS carve-ups: vm_conv_proj_plan.h)
 
 // ---------------------------------------------------------------- conv + x_proj partials
 template <int NB>  // NB = e_pad / 16 output row blocks of x_proj
@@ -271,18 +269,7 @@ __global__ __launch_bounds__(256) void conv_state_cm_kernel(const ConvProjCmPara
 }
 
 // ================================================================ token-major split-K
-constexpr int kTmPitch = 136;  // LDS row pitch in bf16 (272 B): 128 channels + 16-B pad
-constexpr int kSkCh = 128;     // channels per split (fixed: see the file header)
-// conv-state rows staged per tile: sequences whose first 3 steps touch a 64-token tile
-// (out_len >= 8: at most 64 / 8 + 1)
-constexpr int kSkCsRows = kCmTok / 8 + 1;
 constexpr int kSkCsLoads = (kSkCsRows * 3 * kSkCh + 255) / 256;
-
-struct SkTmParams {
-  ConvProjTmArgs a;
-  float* part;  // [nsplit][ntok][ep] fp32 partials of x_dbl, ep = round_up(e, 4)
-  int ntok, nsplit, ep;
-};
 
 // x tile rows tok0 - 8 .. tok0 + 63 (zero outside [0, ntok)), channels c0 .. c0 + 127.
 // Latency shape (what bounds these kernels at B = 1, where a CU holds ~2 workgroups and
@@ -293,9 +280,9 @@ __global__ __launch_bounds__(256) void conv_xproj_tm_kernel(const SkTmParams q) 
   const ConvProjTmArgs& p = q.a;
   extern __shared__ __attribute__((aligned(16))) bf16_t sm[];
   bf16_t* sX = sm;                         // [72][kTmPitch]
-  bf16_t* sU = sX + 72 * kTmPitch;         // [64][kTmPitch]
-  bf16_t* sW = sU + kCmTok * kTmPitch;     // [e_pad][kTmPitch]
-  float* sC = reinterpret_cast<float*>(sW + p.e_pad * kTmPitch);  // [kSkCsRows][3][128]
+  bf16_t* sU = sm + sk_u_off();            // [64][kTmPitch]
+  bf16_t* sW = sm + sk_w_off();            // [e_pad][kTmPitch]
+  float* sC = reinterpret_cast<float*>(sm + sk_c_off(p.e_pad));  // [kSkCsRows][3][128]
   const int tid = threadIdx.x;
   const int lane = tid & 63;
   const int wave = tid >> 6;
@@ -333,7 +320,6 @@ __global__ __launch_bounds__(256) void conv_xproj_tm_kernel(const SkTmParams q) 
   float wl[4], wh[4];
 #pragma unroll
   for (int k = 0; k < 4; ++k) {
-    static_assert(4 * 16 * kSkMaxEp * 4 <= 72 * kTmPitch * 2, "partial rows exceed the x tile");
     wl[k] = k >= 4 - W ? p.cw[c * W + k - (4 - W)] : 0.0f;
     wh[k] = k >= 4 - W ? p.cw[(c + 1) * W + k - (4 - W)] : 0.0f;
   }
@@ -629,11 +615,7 @@ __global__ __launch_bounds__(256) void xdbl_dt_tm_kernel(const SkTmParams q) {
 //   Loads: every global load of a wave (19 x-rows of its 128 channels, its W_x fragments,
 //   conv taps, the conv-state taps of a sequence start) is issued in one round; W_dt
 //   fragments are issued right after the x_proj MFMAs and land during the LDS reduction.
-constexpr int kFuTok = 16;     // token rows per workgroup
-constexpr int kFuMaxSpl = 9;   // splits (waves) per workgroup: dim <= 1152
-constexpr int kFuUPitch = 136; // bf16 pitch of a wave's [16 tok][128 ch] u tile
-constexpr int kFuXdPitch = 72; // bf16 pitch of the [16 tok][64] x_dbl[:R] operand
-constexpr int kFuXRows = 20;   // x rows staged per wave (tok0 - 3 .. tok0 + 16)
+// (kFuTok = 16 token rows, kFuMaxSpl = 9 waves: vm_conv_proj_plan.h)
 
 // Workgroup barrier over LDS traffic only: __syncthreads() also waits vmcnt(0), which
 // drained the W_dt fragment loads (issued to land during the partial reduction) and every
@@ -653,9 +635,7 @@ __global__ __launch_bounds__(64 * kFuMaxSpl) void conv_proj_fused_kernel(const S
   // LDS: per-wave u tiles, then (aliased) the split partials [split][tok][ep], then
   // (aliased) the dt tile [tok][dim]; the x_dbl operand after them
   extern __shared__ __attribute__((aligned(16))) char fsm[];
-  constexpr int kUBytes = kFuMaxSpl * kFuTok * kFuUPitch * 2;
-  constexpr int kPBytes = kFuMaxSpl * kFuTok * kSkMaxEp * 4;
-  constexpr int kArea = kUBytes > kPBytes ? kUBytes : kPBytes;
+  constexpr int kArea = fu_area_bytes();
   bf16_t* sU = reinterpret_cast<bf16_t*>(fsm);
   float* sP = reinterpret_cast<float*>(fsm);
   bf16_t* sXD = reinterpret_cast<bf16_t*>(fsm + kArea);
@@ -738,7 +718,7 @@ __global__ __launch_bounds__(64 * kFuMaxSpl) void conv_proj_fused_kernel(const S
   // backed up; per-wave stamps, scripts/diag/stamp_conv_proj.py --waves).  Rows outside
   // [0, ntok) read as zero or hold stale bytes: their taps are replaced (sequence starts
   // take the conv state) or their outputs dropped (tokens past ntok).
-  char* sXw = fsm + kArea + kFuTok * kFuXdPitch * 2 + wave * (kFuXRows * 256);
+  char* sXw = fsm + fu_xrows_off() + wave * (kFuXRows * 256);
 #pragma unroll
   for (int i = 0; i < kFuXRows / 4; ++i) {
     const int row = 4 * i + (lane >> 4);
@@ -812,7 +792,7 @@ __global__ __launch_bounds__(64 * kFuMaxSpl) void conv_proj_fused_kernel(const S
           wp[k], fp2{__uint_as_float(xw[i + k] << 16), __uint_as_float(xw[i + k] & 0xffff0000u)}, acc2);
     float al = acc2.x, ah = acc2.y;
     int st = s0 + i;
-    if (st >= p.out_len) st -= p.out_len;  // out_len >= 16: at most one wrap
+    if (st >= p.out_len) st -= p.out_len;  // out_len >= 24: at most one wrap
     if (st < 3) {  // uniform: the taps before the sequence start come from the old state
       al = bl;
       ah = bh;
@@ -974,108 +954,56 @@ __global__ __launch_bounds__(64 * kFuMaxSpl) void conv_proj_fused_kernel(const S
   write_conv_state();
 }
 
-bool conv_proj_fused_ok(const ConvProjTmArgs& a) {
-  // e_pad <= 80 (R + 2N <= 80, every VideoMamba size up to d_model 768): wider x_proj
-  // outputs exceed the register budget of the 576-thread workgroup; buffer byte offsets
-  // (x and u rows) must fit 31 bits
-  const long long ntok = static_cast<long long>(a.batch) * a.out_len;
-  return a.dim <= kFuMaxSpl * kSkCh && a.out_len >= 24 && a.e_pad <= 80 &&
-         (a.e + 3) / 4 * 4 <= kSkMaxEp && (a.wdt == nullptr || a.r_pad <= 64) &&
-         (ntok + 3) * a.x_tl * 2 < (1ll << 31) && (ntok + 3) * a.u_tl * 2 < (1ll << 31);
-}
-
-void conv_proj_fused_launch(const ConvProjTmArgs& a, hipStream_t s) {
-  SkTmParams q{};
-  q.a = a;
-  q.part = nullptr;
-  q.ntok = a.batch * a.out_len;
-  q.nsplit = (a.dim + kSkCh - 1) / kSkCh;
-  q.ep = (a.e + 3) / 4 * 4;
-  const unsigned tiles = static_cast<unsigned>((q.ntok + kFuTok - 1) / kFuTok);
-  constexpr int kUBytes = kFuMaxSpl * kFuTok * kFuUPitch * 2;
-  constexpr int kPBytes = kFuMaxSpl * kFuTok * kSkMaxEp * 4;
-  const size_t lds = static_cast<size_t>(kUBytes > kPBytes ? kUBytes : kPBytes) +
-                     kFuTok * kFuXdPitch * 2 + kFuMaxSpl * kFuXRows * 256;
-  static_assert(kFuTok * (kFuMaxSpl * kSkCh + 8) * 2 <= kPBytes, "dt tile exceeds the area");
-  const dim3 grid(tiles), block(64 * q.nsplit);
-  const bool cs32 = a.csi != nullptr && a.csi_dtype != VM_DTYPE_BF16;
-  switch (a.e_pad / 16) {
+void conv_proj_fused_launch(const SkTmParams& q, const ConvProjPlan& pl, hipStream_t s) {
+  const dim3 grid(pl.main.gx), block(pl.main.block);
+  switch (pl.NB) {
 #define VM_FU_CASE(NBV)                                                                    \
     case NBV:                                                                              \
-      if (cs32) hipLaunchKernelGGL((conv_proj_fused_kernel<NBV, true>), grid, block, lds, s, q); \
-      else hipLaunchKernelGGL((conv_proj_fused_kernel<NBV, false>), grid, block, lds, s, q);   \
+      if (pl.CS32) hipLaunchKernelGGL((conv_proj_fused_kernel<NBV, true>), grid, block, pl.main.lds, s, q); \
+      else hipLaunchKernelGGL((conv_proj_fused_kernel<NBV, false>), grid, block, pl.main.lds, s, q);   \
       break;
     VM_FU_CASE(1) VM_FU_CASE(2) VM_FU_CASE(3) VM_FU_CASE(4) VM_FU_CASE(5)
 #undef VM_FU_CASE
   }
 }
 
-long long conv_proj_sk_workspace_bytes(int batch, int out_len, int dim, int e) {
-  if (batch <= 0 || out_len <= 0 || dim <= 0 || e <= 0) return 0;
-  const long long ntok = 1LL * batch * out_len;
-  const long long nsplit = (dim + kSkCh - 1) / kSkCh;
-  return nsplit * ntok * ((e + 3) / 4 * 4) * static_cast<long long>(sizeof(float));
-}
-
-void conv_proj_sk_launch(const ConvProjTmArgs& a, float* part, hipStream_t s) {
-  SkTmParams q{};
-  q.a = a;
-  q.part = part;
-  q.ntok = a.batch * a.out_len;
-  q.nsplit = (a.dim + kSkCh - 1) / kSkCh;
-  q.ep = (a.e + 3) / 4 * 4;
-  const unsigned tiles = static_cast<unsigned>((q.ntok + kCmTok - 1) / kCmTok);
-  const size_t lds = static_cast<size_t>(72 + kCmTok + a.e_pad) * kTmPitch * sizeof(bf16_t) +
-                    static_cast<size_t>(kSkCsRows) * 3 * kSkCh * sizeof(float);
-  dim3 g1(tiles, q.nsplit);
-  switch (a.e_pad / 16) {
+void conv_proj_sk_launch(const SkTmParams& q, const ConvProjPlan& pl, hipStream_t s) {
+  const dim3 g1(pl.main.gx, pl.main.gy);
+  switch (pl.NB) {
 #define VM_SK_CASE(NBV) \
-    case NBV: hipLaunchKernelGGL(conv_xproj_tm_kernel<NBV>, g1, dim3(256), lds, s, q); break;
+    case NBV: hipLaunchKernelGGL(conv_xproj_tm_kernel<NBV>, g1, dim3(pl.main.block), pl.main.lds, s, q); break;
     VM_SK_CASE(1) VM_SK_CASE(2) VM_SK_CASE(3) VM_SK_CASE(4)
     VM_SK_CASE(5) VM_SK_CASE(6) VM_SK_CASE(7) VM_SK_CASE(8)
 #undef VM_SK_CASE
   }
-  conv_proj_sk_reduce_launch(a, part, s);
+  conv_proj_sk_reduce_launch(q, pl, s);
 }
 
 // The split-K form's second kernel alone: x_dbl from the partials, dt_proj (a.wdt) — also
 // the tail of vm_in_proj_conv_proj_fwd, whose in_proj epilogue writes the same partials.
-void conv_proj_sk_reduce_launch(const ConvProjTmArgs& a, float* part, hipStream_t s) {
-  SkTmParams q{};
-  q.a = a;
-  q.part = part;
-  q.ntok = a.batch * a.out_len;
-  q.nsplit = (a.dim + kSkCh - 1) / kSkCh;
-  q.ep = (a.e + 3) / 4 * 4;
-  const unsigned tiles = static_cast<unsigned>((q.ntok + kCmTok - 1) / kCmTok);
-  const unsigned cblocks = a.wdt ? static_cast<unsigned>((a.dim + 127) / 128) : 1u;
-  const dim3 g2(tiles, cblocks);
-  switch (q.nsplit) {
-#define VM_SK2(NS) case NS: hipLaunchKernelGGL(xdbl_dt_tm_kernel<NS>, g2, dim3(256), 0, s, q); break;
+void conv_proj_sk_reduce_launch(const SkTmParams& q, const ConvProjPlan& pl, hipStream_t s) {
+  const dim3 g2(pl.reduce.gx, pl.reduce.gy);
+  switch (pl.NSPL) {
+#define VM_SK2(NS) case NS: hipLaunchKernelGGL(xdbl_dt_tm_kernel<NS>, g2, dim3(pl.reduce.block), 0, s, q); break;
     VM_SK2(1) VM_SK2(2) VM_SK2(3) VM_SK2(4) VM_SK2(5) VM_SK2(6) VM_SK2(7) VM_SK2(8)
     VM_SK2(9) VM_SK2(10) VM_SK2(11) VM_SK2(12) VM_SK2(13) VM_SK2(14) VM_SK2(15) VM_SK2(16)
 #undef VM_SK2
   }
 }
 
-// Split count: a FIXED channel split (128 channels per split) so the x_proj reduction order,
-// and with it every token's x_dbl bits, never depends on the token count — a chunk-
-// dependent split (more splits for shorter sequences) broke chunked == full bitwise.
-// At B = 1 (3,144 tokens, D = 1152) that is 49 x 9 = 441 workgroups.
-constexpr int kCmSplitCh = 128;
-static int cm_splits(int ntok, int dim) {
-  (void)ntok;
-  return (dim + kCmSplitCh - 1) / kCmSplitCh;
-}
-
 }  // namespace vm
 
 using namespace vm;
 
+static ConvProjPlanIn cm_plan_in(int batch, int out_len, int dim, int e) {
+  ConvProjPlanIn in{};
+  in.layout = ConvProjLayout::kChannelMajor;
+  in.batch = batch; in.out_len = out_len; in.dim = dim; in.e = e;
+  return in;
+}
+
 extern "C" long long vm_conv_proj_cm_workspace_bytes(int batch, int out_len, int dim, int e) {
-  if (batch <= 0 || out_len <= 0 || dim <= 0 || dim % 64 != 0 || e <= 0) return 0;
-  const int ntok = batch * out_len;
-  return static_cast<long long>(cm_splits(ntok, dim)) * e * ntok * sizeof(float);
+  return plan_conv_proj(cm_plan_in(batch, out_len, dim, e)).ws_query;
 }
 
 extern "C" int vm_conv_proj_cm_fwd(const void* xz, long long x_sd,
@@ -1088,10 +1016,9 @@ extern "C" int vm_conv_proj_cm_fwd(const void* xz, long long x_sd,
                                    void* dt, long long dt_sd, int out_len, int batch, int dim,
                                    int seqlen, int width, void* workspace,
                                    long long workspace_bytes, vm_stream_t stream) {
-  if (!xz || !conv_weight || !wx_pad || !wdt_pad || !u || !xdbl || !dt) {
-    vmhost::set_error("vm_conv_proj_cm_fwd: null required pointer");
-    return VM_E_INVALID;
-  }
+  static const char* const kEntry = "vm_conv_proj_cm_fwd";
+  if (!xz || !conv_weight || !wx_pad || !wdt_pad || !u || !xdbl || !dt)
+    return conv_proj_refuse(kEntry, kConvProjNull);
   if (batch < 0 || dim <= 0 || dim % 64 != 0 || seqlen < 1 || out_len < seqlen || out_len % 8 ||
       width < 1 || width > 4 || e < 1 || e_pad % 16 != 0 || e_pad < e || e_pad > 128 ||
       r < 1 || r > e || (r_pad != 32 && r_pad != 64) || r_pad < r ||
@@ -1105,14 +1032,14 @@ extern "C" int vm_conv_proj_cm_fwd(const void* xz, long long x_sd,
     vmhost::set_error("vm_conv_proj_cm_fwd: x / u / dt rows and the weights must be 16-byte aligned");
     return VM_E_INVALID;
   }
-  if (cs_out && cs_in == cs_out) {
-    vmhost::set_error("vm_conv_proj_cm_fwd: conv_state_out must not alias conv_state_in");
-    return VM_E_INVALID;
-  }
+  if (cs_out && cs_in == cs_out) return conv_proj_refuse(kEntry, kConvProjAlias);
   if (batch == 0) return VM_OK;
-  const long long need = vm_conv_proj_cm_workspace_bytes(batch, out_len, dim, e);
-  if (!workspace || workspace_bytes < need) {
-    vmhost::set_error("vm_conv_proj_cm_fwd: workspace of %lld bytes required", need);
+  ConvProjPlanIn in = cm_plan_in(batch, out_len, dim, e);
+  in.seqlen = seqlen; in.e_pad = e_pad; in.r = r; in.r_pad = r_pad; in.width = width;
+  in.want_dt = true; in.has_cs_in = cs_in != nullptr; in.has_cs_out = cs_out != nullptr;
+  const ConvProjPlan pl = plan_conv_proj(in);
+  if (!workspace || workspace_bytes < pl.ws_need) {
+    vmhost::set_error("vm_conv_proj_cm_fwd: workspace of %lld bytes required", pl.ws_need);
     return VM_E_INVALID;
   }
   ConvProjCmParams p{};
@@ -1123,23 +1050,24 @@ extern "C" int vm_conv_proj_cm_fwd(const void* xz, long long x_sd,
   p.part = static_cast<float*>(workspace);
   p.x_sd = x_sd; p.u_sd = u_sd; p.xd_sd = xd_sd; p.dt_sd = dt_sd;
   p.csi_sb = csi_sb; p.csi_sd = csi_sd; p.cso_sb = cso_sb; p.cso_sd = cso_sd;
-  p.batch = batch; p.dim = dim; p.seqlen = seqlen; p.lp = out_len; p.ntok = batch * out_len;
+  p.batch = batch; p.dim = dim; p.seqlen = seqlen; p.lp = out_len; p.ntok = pl.ntok;
   p.e = e; p.e_pad = e_pad; p.r = r; p.r_pad = r_pad; p.width = width;
   p.csi_dtype = cs_in_dtype; p.cso_dtype = cs_out_dtype;
-  p.nsplit = cm_splits(p.ntok, dim);
-  p.split_ch = kCmSplitCh;
+  p.nsplit = pl.nsplit;
+  p.split_ch = kSkCh;
   hipStream_t st = static_cast<hipStream_t>(stream);
-  const unsigned tiles = static_cast<unsigned>((p.ntok + kCmTok - 1) / kCmTok);
-  dim3 g1(tiles, p.nsplit);
-  switch (e_pad / 16) {
+  const dim3 g1(pl.main.gx, pl.main.gy);
+  switch (pl.NB) {
 #define VM_CM_CASE(NBV) \
-    case NBV: hipLaunchKernelGGL(conv_xproj_cm_kernel<NBV>, g1, dim3(256), 0, st, p); break;
+    case NBV: hipLaunchKernelGGL(conv_xproj_cm_kernel<NBV>, g1, dim3(pl.main.block), 0, st, p); break;
     VM_CM_CASE(1) VM_CM_CASE(2) VM_CM_CASE(3) VM_CM_CASE(4)
     VM_CM_CASE(5) VM_CM_CASE(6) VM_CM_CASE(7) VM_CM_CASE(8)
 #undef VM_CM_CASE
   }
-  hipLaunchKernelGGL(xdbl_dt_cm_kernel, dim3(tiles, (dim + 127) / 128), dim3(256), 0, st, p);
-  if (cs_out)
-    hipLaunchKernelGGL(conv_state_cm_kernel, dim3((dim + 255) / 256, batch), dim3(256), 0, st, p);
-  return vmhost::launch_status("vm_conv_proj_cm_fwd");
+  hipLaunchKernelGGL(xdbl_dt_cm_kernel, dim3(pl.reduce.gx, pl.reduce.gy), dim3(pl.reduce.block), 0,
+                     st, p);
+  if (pl.state.gx)
+    hipLaunchKernelGGL(conv_state_cm_kernel, dim3(pl.state.gx, pl.state.gy), dim3(pl.state.block), 0,
+                       st, p);
+  return vmhost::launch_status(kEntry);
 }

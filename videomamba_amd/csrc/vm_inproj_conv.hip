@@ -44,17 +44,7 @@ struct InConvParams {
   int nxr, nzr;                    // x row tiles (112 rows), z row tiles (128 rows)
 };
 
-constexpr int kIcRow = 128;                  // bytes per staged K row (64 bf16)
-constexpr int kIcOut = 112;                  // x output rows per tile
-constexpr int kIcHalo = 16;                  // rows above them computed for the conv
-constexpr int kIcPitch = 136;                // bf16 pitch of the LDS x / u tile
-constexpr int kIcCsSeq = 3;                  // sequences starting in a tile (out_len >= 56)
-constexpr int kIcStage = (128 + 128) * kIcRow;  // one K-step stage: A and B rows
-constexpr int kIcOBytes = 128 * kIcPitch * 2;   // x tile [128][kIcPitch] bf16
-constexpr int kIcWBytes = 80 * kIcPitch * 2;    // W_x slice [e_pad <= 80][kIcPitch]
-constexpr int kIcCBytes = kIcCsSeq * 3 * 128 * 4;
-constexpr int kIcLds = (2 * kIcStage > kIcOBytes + kIcWBytes + kIcCBytes)
-                           ? 2 * kIcStage : kIcOBytes + kIcWBytes + kIcCBytes;
+// (tile geometry and the kIc* LDS byte sizes: vm_conv_proj_plan.h)
 
 __device__ __forceinline__ int ic_slot(int row, int chunk) { return chunk ^ ((row >> 1) & 7); }
 
@@ -443,50 +433,24 @@ __global__ __launch_bounds__(256) void xdbl_reduce_kernel(const InConvParams q) 
     if (e0 + kk < p.e) dst[kk] = from_f32<bf16_t>(sv[kk]);
 }
 
-bool inproj_conv_ok(int k, const ConvProjTmArgs& a) {
-  switch (k / 64) {
-    case 3: case 6: case 9: case 12: case 18: case 24: break;
-    default: return false;
-  }
-  const long long ntok = static_cast<long long>(a.batch) * a.out_len;
-  return k % 64 == 0 && a.batch >= 1 && a.batch <= kSkMaxBatch && a.dim % 128 == 0 &&
-         a.dim <= 2048 && a.out_len >= 56 && a.e_pad <= 80 && a.e_pad % 16 == 0 &&
-         (a.e + 3) / 4 * 4 <= kSkMaxEp && (a.wdt == nullptr || a.r_pad <= 64) &&
-         a.width >= 1 && a.width <= 4 && ntok * a.u_tl * 2 < (1ll << 31);
-}
-
-void inproj_conv_launch(const InConvParams& q0, hipStream_t s) {
-  InConvParams q = q0;
-  const unsigned grid = static_cast<unsigned>((q.nxr + q.nzr) * q.nsplit);
-  const size_t lds = kIcLds;
-  switch ((q.k / 64) * 16 + q.a.e_pad / 16) {
-#define VM_IC(NKV, NBV)                                                                    \
-    case NKV * 16 + NBV:                                                                   \
-      hipLaunchKernelGGL((inproj_conv_kernel<NKV, NBV>), dim3(grid), dim3(512), lds, s, q); \
-      break;
-#define VM_IC_K(NKV) VM_IC(NKV, 1) VM_IC(NKV, 2) VM_IC(NKV, 3) VM_IC(NKV, 4) VM_IC(NKV, 5)
-    VM_IC_K(3) VM_IC_K(6) VM_IC_K(9) VM_IC_K(12) VM_IC_K(18) VM_IC_K(24)
-#undef VM_IC_K
-#undef VM_IC
-    default: break;
-  }
-}
-
 }  // namespace vm
 
 using namespace vm;
 
 extern "C" long long vm_in_proj_conv_proj_workspace_bytes(int batch, int out_len, int dim, int e) {
-  return conv_proj_sk_workspace_bytes(batch, out_len, dim, e);
+  ConvProjPlanIn in{};
+  in.entry = ConvProjEntry::kInProjConvProj;
+  in.batch = batch; in.out_len = out_len; in.dim = dim; in.e = e;
+  return plan_conv_proj(in).ws_query;
 }
 
 extern "C" int vm_in_proj_conv_proj_fits(int k, int batch, int out_len, int dim, int e, int e_pad,
                                          int r_pad, int width, int has_dt) {
-  ConvProjTmArgs a{};
-  a.batch = batch; a.out_len = out_len; a.dim = dim; a.e = e; a.e_pad = e_pad;
-  a.r_pad = r_pad; a.width = width; a.u_tl = dim;
-  a.wdt = has_dt ? reinterpret_cast<const bf16_t*>(16) : nullptr;
-  return inproj_conv_ok(k, a) ? 1 : 0;
+  ConvProjPlanIn in{};
+  in.entry = ConvProjEntry::kInProjConvProj;
+  in.batch = batch; in.out_len = out_len; in.dim = dim; in.e = e; in.e_pad = e_pad;
+  in.r_pad = r_pad; in.width = width; in.u_sl = dim; in.want_dt = has_dt != 0; in.k = k;
+  return plan_conv_proj(in).form == ConvProjForm::kInProj ? 1 : 0;
 }
 
 extern "C" int vm_in_proj_conv_proj_fwd(
@@ -498,21 +462,17 @@ extern "C" int vm_in_proj_conv_proj_fwd(
     void* u, long long u_tl, void* xdbl, long long xd_tl, void* dt, long long dt_tl,
     int out_len, int batch, int dim, int seqlen, int width, void* workspace,
     long long workspace_bytes, vm_stream_t stream) {
-  if (!hn || !w_in || !z || !conv_weight || !wx_pad || !u || !xdbl || (dt && !wdt_pad)) {
-    vmhost::set_error("vm_in_proj_conv_proj_fwd: null required pointer");
-    return VM_E_INVALID;
-  }
-  ConvProjTmArgs a{};
-  a.x = nullptr; a.x_tl = 0; a.cw = conv_weight; a.cb = conv_bias;
-  a.csi = cs_in; a.csi_dtype = cs_in_dtype; a.csi_sb = csi_sb; a.csi_sd = csi_sd;
-  a.cso = cs_out; a.cso_dtype = cs_out_dtype; a.cso_sb = cso_sb; a.cso_sd = cso_sd;
-  a.wx = static_cast<const bf16_t*>(wx_pad); a.e = e; a.e_pad = e_pad;
-  a.wdt = dt ? static_cast<const bf16_t*>(wdt_pad) : nullptr; a.r = r; a.r_pad = r_pad;
-  a.u = static_cast<bf16_t*>(u); a.u_tl = u_tl; a.xdbl = static_cast<bf16_t*>(xdbl);
-  a.xd_tl = xd_tl; a.dt = static_cast<bf16_t*>(dt); a.dt_tl = dt_tl;
-  a.out_len = out_len; a.batch = batch; a.dim = dim; a.seqlen = seqlen; a.width = width;
-  const long long ntok = static_cast<long long>(batch) * out_len;
-  if (!inproj_conv_ok(k, a) || seqlen < 1 || seqlen > out_len || r < 1 || r > e ||
+  static const char* const kEntry = "vm_in_proj_conv_proj_fwd";
+  if (!hn || !w_in || !z || !conv_weight || !wx_pad || !u || !xdbl || (dt && !wdt_pad))
+    return conv_proj_refuse(kEntry, kConvProjNull);
+  const ConvProjTmArgs a = conv_proj_tm_args(
+      nullptr, 0, conv_weight, conv_bias, cs_in, cs_in_dtype, csi_sb, csi_sd, cs_out,
+      cs_out_dtype, cso_sb, cso_sd, wx_pad, e, e_pad, wdt_pad, r, r_pad, u, u_tl, xdbl, xd_tl,
+      dt, dt_tl, out_len, batch, dim, seqlen, width);
+  ConvProjPlanIn in = conv_proj_plan_in(a, ConvProjEntry::kInProjConvProj);
+  in.k = k; in.ldh = ldh; in.ldw = ldw;
+  const ConvProjPlan pl = plan_conv_proj(in);
+  if (pl.form != ConvProjForm::kInProj || seqlen < 1 || seqlen > out_len || r < 1 || r > e ||
       (dt && r_pad != 32 && r_pad != 64) || (cs_in && !vmhost::dtype_ok(cs_in_dtype)) ||
       (cs_out && !vmhost::dtype_ok(cs_out_dtype)) || ldh < k || ldw < k || ldz < dim ||
       ldh % 8 || ldw % 8 || ldz % 8 || u_tl < dim || u_tl % 2 || xd_tl < e || xd_tl % 2 ||
@@ -520,22 +480,17 @@ extern "C" int vm_in_proj_conv_proj_fwd(
       !vmhost::aligned16(hn) || !vmhost::aligned16(w_in) || !vmhost::aligned16(z) ||
       !vmhost::aligned16(wx_pad) || (dt && !vmhost::aligned16(dt)) ||
       (dt && !vmhost::aligned16(wdt_pad)) || (reinterpret_cast<uintptr_t>(u) & 3) ||
-      (reinterpret_cast<uintptr_t>(xdbl) & 3) || ntok * ldh * 2 >= (1ll << 31) ||
-      2ll * dim * ldw * 2 >= (1ll << 31) || ntok > (1 << 30)) {
+      (reinterpret_cast<uintptr_t>(xdbl) & 3)) {
     vmhost::set_error("vm_in_proj_conv_proj_fwd: unsupported shape (bf16; k in {192 .. 1536} "
                       "by 64-steps; batch <= %d, out_len >= 56 and even, dim %% 128 == 0 and "
                       "<= 2048, R + 2N <= %d, e_pad <= 80, width <= 4; 16-byte aligned rows; "
                       "hn under 2 GB)", kSkMaxBatch, kSkMaxEp);
     return VM_E_INVALID;
   }
-  if (cs_out && cs_in == cs_out) {
-    vmhost::set_error("vm_in_proj_conv_proj_fwd: conv_state_out must not alias conv_state_in");
-    return VM_E_INVALID;
-  }
-  const long long need = conv_proj_sk_workspace_bytes(batch, out_len, dim, e);
-  if (!workspace || workspace_bytes < need) {
+  if (cs_out && cs_in == cs_out) return conv_proj_refuse(kEntry, kConvProjAlias);
+  if (!workspace || workspace_bytes < pl.ws_need) {
     vmhost::set_error("vm_in_proj_conv_proj_fwd: needs a workspace of %lld bytes "
-                      "(vm_in_proj_conv_proj_workspace_bytes)", need);
+                      "(vm_in_proj_conv_proj_workspace_bytes)", pl.ws_need);
     return VM_E_INVALID;
   }
   InConvParams q{};
@@ -544,25 +499,32 @@ extern "C" int vm_in_proj_conv_proj_fwd(
   q.z = static_cast<bf16_t*>(z); q.ldz = ldz;
   q.a = a;
   q.part = static_cast<float*>(workspace);
-  q.ntok = static_cast<int>(ntok);
-  q.nsplit = dim / 128;
-  q.ep = (e + 3) / 4 * 4;
+  q.ntok = pl.ntok; q.nsplit = pl.nsplit; q.ep = pl.ep;
   q.k = k;
-  q.nxr = static_cast<int>((ntok + kIcOut - 1) / kIcOut);
-  q.nzr = static_cast<int>((ntok + 127) / 128);
+  q.nxr = pl.nxr; q.nzr = pl.nzr;
   hipStream_t s = static_cast<hipStream_t>(stream);
-  inproj_conv_launch(q, s);
+  const dim3 grid(pl.main.gx), block(pl.main.block);
+  switch (pl.NK * 16 + pl.NB) {
+#define VM_IC(NKV, NBV)                                                                    \
+    case NKV * 16 + NBV:                                                                   \
+      hipLaunchKernelGGL((inproj_conv_kernel<NKV, NBV>), grid, block, pl.main.lds, s, q);  \
+      break;
+#define VM_IC_K(NKV) VM_IC(NKV, 1) VM_IC(NKV, 2) VM_IC(NKV, 3) VM_IC(NKV, 4) VM_IC(NKV, 5)
+    VM_IC_K(3) VM_IC_K(6) VM_IC_K(9) VM_IC_K(12) VM_IC_K(18) VM_IC_K(24)
+#undef VM_IC_K
+#undef VM_IC
+    default: break;
+  }
   if (dt) {
-    conv_proj_sk_reduce_launch(a, q.part, s);
+    conv_proj_sk_reduce_launch(sk_tm_params(a, pl, q.part), pl, s);
   } else {
-    const unsigned blocks = static_cast<unsigned>((ntok * ((e + 3) / 4) + 255) / 256);
-    switch (q.nsplit) {
-#define VM_XR(NS) case NS: hipLaunchKernelGGL(xdbl_reduce_kernel<NS>, dim3(blocks), dim3(256), 0, s, q); break;
+    switch (pl.NSPL) {
+#define VM_XR(NS) case NS: hipLaunchKernelGGL(xdbl_reduce_kernel<NS>, dim3(pl.reduce.gx), dim3(pl.reduce.block), 0, s, q); break;
       VM_XR(1) VM_XR(2) VM_XR(3) VM_XR(4) VM_XR(5) VM_XR(6) VM_XR(7) VM_XR(8)
       VM_XR(9) VM_XR(10) VM_XR(11) VM_XR(12) VM_XR(13) VM_XR(14) VM_XR(15) VM_XR(16)
 #undef VM_XR
       default: break;
     }
   }
-  return vmhost::launch_status("vm_in_proj_conv_proj_fwd");
+  return vmhost::launch_status(kEntry);
 }

@@ -347,6 +347,7 @@ def scan_chunk_steps(batch: int, dim: int, seqlen: int, dstate: int, segments: i
 
 
 SCAN_DTPROJ_MAX_SEGMENT = 64  # the segmented dt_proj-in-scan form (ABI v11)
+CONV_PROJ_SMALL_MAX_BATCH = 8  # the small-batch conv_proj forms (vm_conv_proj_plan.h kSkMaxBatch)
 _SCAN_CHUNK_SEGS_PER_BLOCK = 8  # segments per workgroup of the chunked scan (vm_scan_plan.h kChW)
 _CU_COUNT = {}
 

@@ -350,7 +350,7 @@ class Mamba(nn.Module):
             computes its dt exactly as conv_proj's dt_proj would (ABI v11), so the bits are the
             ones conv_proj writes otherwise — the choice never changes a result, and chunked
             == full stays exact whichever form a chunk length selects; or
-          * the single-pass scan (D % 128 == 0) above the split-K batch (> 8 clips; "on":
+          * the single-pass scan (D % 128 == 0) above K.CONV_PROJ_SMALL_MAX_BATCH (> 8 clips; "on":
             at any batch), whose 16-step MFMA dt blocks are its own arithmetic — below 9
             clips a short sequence's single pass keeps conv_proj's dt for the same
             invariance."""
@@ -367,7 +367,7 @@ class Mamba(nn.Module):
                 return steps <= K.SCAN_DTPROJ_MAX_SEGMENT
             return K.scan_dtproj_segmented_pays(Bsz, self.d_inner, seqlen, self.d_state,
                                                 hn.device)
-        if mode == "auto" and Bsz <= 8:
+        if mode == "auto" and Bsz <= K.CONV_PROJ_SMALL_MAX_BATCH:
             return False
         return self.d_inner % 128 == 0
 

@@ -18,6 +18,8 @@
  *   vm_selective_state_update  <- mamba_ssm selective_state_update  (mamba_simple.py:483-494)
  *   vm_causal_conv1d_fwd       <- causal_conv1d_fn (+ conv_state prepend)
  *                                 (mamba_simple.py:381-404)
+ *   vm_causal_conv1d_bwd       <- the backward of causal_conv1d_fn
+ *                                 (mamba_simple.py:381-404 under autograd)
  *   vm_causal_conv1d_update    <- causal_conv1d_update  (mamba_simple.py:468-474)
  *   vm_conv_proj_fwd           <- causal_conv1d_fn + x_proj + dt_proj, fused, token-major
  *                                 (mamba_simple.py:381-416)
@@ -28,6 +30,8 @@
  *                                 layout (mamba_simple.py:381-416)
  *   vm_add_norm_fwd            <- mamba_ssm rms_norm_fn / layer_norm_fn
  *                                 (models/videomamba/videomamba.py:152-166, :904-918)
+ *   vm_add_norm_bwd            <- the backward of rms_norm_fn / layer_norm_fn
+ *                                 (videomamba.py:152-166, :904-918 under autograd)
  *   vm_norm_pool_fwd           <- final add + norm (videomamba.py:896-918) with the
  *                                 per-frame / whole-clip column sums of the pooling
  *   vm_pool_finish_fwd         <- the pooling tail: means, CLS add / concat and pool_norm
@@ -62,7 +66,7 @@
 extern "C" {
 #endif
 
-#define VM_ABI_VERSION 15
+#define VM_ABI_VERSION 16
 
 #define VM_DTYPE_F32 0
 #define VM_DTYPE_BF16 1
@@ -296,6 +300,42 @@ int vm_causal_conv1d_fwd(const void* x, long long x_sb, long long x_sd, long lon
                          vm_stream_t stream);
 
 /*
+ * Causal conv1d backward (ABI v16): the gradient of vm_causal_conv1d_fwd for token-major
+ * operands, what causal-conv1d's differentiable causal_conv1d_fn supplies.  x, weight, bias,
+ * cs_in, width and silu are the forward's inputs, passed exactly as to the forward; nothing the
+ * forward computed is needed.  With e = [cs_in | x]:
+ *   pre[t] = bias + sum_i w[i] e[t - width + 1 + i];  dpre = dout silu'(pre) (dout without SiLU)
+ *   de[j] = sum_i w[i] dpre[j + width - 1 - i] over the steps that exist.
+ *   dout:    (batch, dim, seqlen) in `dtype`, the gradient of out.
+ * Outputs, every one overwritten (never accumulated into):
+ *   dx:      (batch, dim, seqlen) in `dtype`, rounded once at the store;
+ *   dcs_in:  (batch, dim, width) fp32 strides (sb, sd, 1), nullable; its slot 0 is always 0
+ *            (no tap reaches the oldest state entry);
+ *   dweight: (dim, width) fp32 contiguous;  dbias: (dim) fp32, NULL iff bias NULL.
+ * Token-major only: unit channel stride for x / dout / dx; width <= 4; fp32 or bf16 with all
+ * arithmetic in fp32.  A null required pointer, another stride, width or dtype, dbias without
+ * bias (or bias without dbias) and a workspace below vm_causal_conv1d_bwd_workspace_bytes return
+ * VM_E_INVALID before any launch.  Deterministic: no atomics; every workgroup writes the
+ * dweight / dbias sums of its (batch row, 61-step time tile) to the workspace as fp32 partials
+ * and a second kernel adds them: 16 contiguous ranges of parts, each in index order, then the
+ * range sums in range order.  The ranges depend on (batch, seqlen) alone, not on the device.
+ */
+int vm_causal_conv1d_bwd(const void* x, long long x_sb, long long x_sd, long long x_sl,
+                         const float* weight, const float* bias,
+                         const void* cs_in, int cs_in_dtype, long long csi_sb, long long csi_sd,
+                         const void* dout, long long do_sb, long long do_sd, long long do_sl,
+                         void* dx, long long dx_sb, long long dx_sd, long long dx_sl,
+                         float* dcs_in, long long dcs_sb, long long dcs_sd,
+                         float* dweight, float* dbias,
+                         int batch, int dim, int seqlen, int width, int silu, int dtype,
+                         void* workspace, long long workspace_bytes, vm_stream_t stream);
+
+/* Workspace bytes vm_causal_conv1d_bwd needs for this shape: (width + 1) fp32 partial rows of
+ * dpad = round_up(dim, 64) channels per (batch row, time tile) — at most
+ * 20 batch dpad (seqlen / 61 + 1).  Pure host code (no HIP call). */
+long long vm_causal_conv1d_bwd_workspace_bytes(int batch, int dim, int seqlen, int width);
+
+/*
  * Fused token-major mixer middle (bf16): per token row of the flattened (batch, out_len)
  * axis,  u = silu(conv1d([conv_state_in | x]))  ->  x_dbl = u @ W_x^T  ->
  * dt = x_dbl[:, :r] @ W_dt^T, rounded to bf16 at each of the three (the reference's
@@ -418,6 +458,43 @@ int vm_add_norm_fwd(const void* x, int x_dtype, const void* residual, int res_dt
                     const float* weight, const float* bias, void* out, int out_dtype,
                     void* residual_out, int res_out_dtype, long long rows, int cols,
                     float eps, int is_rms, vm_stream_t stream);
+
+/*
+ * Add + norm backward (ABI v16): the gradient of vm_add_norm_fwd, what mamba_ssm's
+ * differentiable rms_norm_fn / layer_norm_fn supply.
+ *   s:        (rows, cols) contiguous in s_dtype, the pre-norm sum the forward wrote as
+ *             residual_out.  Statistics are recomputed from it (the forward's own when fp32);
+ *   weight:   (cols) fp32;  bias: the forward's bias pointer — only whether it is NULL is used;
+ *   dy:       (rows, cols) contiguous in dy_dtype, the gradient of out;
+ *   dres_out: (rows, cols) contiguous in s_dtype, the gradient arriving at residual_out,
+ *             NULL = 0;  eps, is_rms as in the forward.
+ * With xhat = (s - mean) rstd and g = dy weight:
+ *   RMSNorm ds = rstd (g - xhat mean(g xhat));  LayerNorm ds = rstd (g - mean(g) - xhat mean(g xhat))
+ *   ds += dres_out.
+ * Outputs, every one overwritten:
+ *   dx:        (rows, cols) in dx_dtype;  dresidual: nullable, in dres_dtype — the same values
+ *              as dx, each rounded once to its own dtype;
+ *   dweight:   (cols) fp32 = sum_rows dy xhat;  dbias: (cols) fp32 = sum_rows dy, NULL iff bias
+ *              NULL.
+ * cols <= 2048, any cols (a vector path for cols % 4 == 0 and 16-byte aligned buffers).  A null
+ * required pointer, another dtype, cols out of range, dbias without bias (or bias without
+ * dbias) and a workspace below vm_add_norm_bwd_workspace_bytes return VM_E_INVALID before any
+ * launch.  Deterministic: no atomics; every workgroup (one wave) owns a fixed contiguous range
+ * of rows, adds its column partials in row order and writes them to the workspace; a second
+ * kernel adds them: 16 contiguous ranges of workgroups, each in workgroup order, then the range
+ * sums in range order.  The row ranges depend on (rows, cols) alone, not on the device.
+ */
+int vm_add_norm_bwd(const void* s, int s_dtype, const float* weight, const float* bias,
+                    const void* dy, int dy_dtype, const void* dres_out,
+                    void* dx, int dx_dtype, void* dresidual, int dres_dtype,
+                    float* dweight, float* dbias, long long rows, int cols, float eps,
+                    int is_rms, void* workspace, long long workspace_bytes, vm_stream_t stream);
+
+/* Workspace bytes vm_add_norm_bwd needs for this shape (0 when cols > 2048, which the entry
+ * refuses): two fp32 partial rows of cpad = round_up(cols, 64) columns per workgroup, with at
+ * most min(2048, rows / 4 + 1) workgroups — at most 8 cpad min(2048, rows / 4 + 1).  Pure host
+ * code (no HIP call). */
+long long vm_add_norm_bwd_workspace_bytes(long long rows, int cols);
 
 /*
  * Final add + norm fused with the pooling front half.  Per batch row b, rows

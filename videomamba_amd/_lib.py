@@ -20,7 +20,7 @@ LIB_PATH = os.path.join(os.path.dirname(os.path.abspath(__file__)), LIB_NAME)
 
 VM_DTYPE_F32 = 0
 VM_DTYPE_BF16 = 1
-ABI_VERSION = 15
+ABI_VERSION = 16
 
 _P = c_void_p
 _LL = c_longlong
@@ -96,6 +96,15 @@ _SIGNATURES = {
     "vm_causal_conv1d_fwd": (
         [_P, _LL, _LL, _LL, _P, _P, _P, _I, _LL, _LL, _P, _I, _LL, _LL, _P, _LL, _LL, _LL, _I,
          _I, _I, _I, _I, _I, _I, _P], _I),
+    "vm_causal_conv1d_bwd": (
+        [_P, _LL, _LL, _LL, _P, _P,               # x (sb, sd, sl), weight, bias
+         _P, _I, _LL, _LL,                        # cs_in, dtype (sb, sd)
+         _P, _LL, _LL, _LL,                       # dout
+         _P, _LL, _LL, _LL,                       # dx
+         _P, _LL, _LL, _P, _P,                    # dcs_in (sb, sd), dweight, dbias
+         _I, _I, _I, _I, _I, _I,                  # batch, dim, seqlen, width, silu, dtype
+         _P, _LL, _P], _I),                       # workspace, bytes, stream
+    "vm_causal_conv1d_bwd_workspace_bytes": ([_I, _I, _I, _I], _LL),
     "vm_conv_proj_fwd": (
         [_P, _LL, _LL, _P, _P,                    # xz, conv weight / bias
          _P, _I, _LL, _LL, _P, _I, _LL, _LL,      # conv state in / out
@@ -130,6 +139,13 @@ _SIGNATURES = {
         [_P, _LL, _P, _I, _LL, _LL, _P, _P, _P, _LL, _I, _I, _I, _I, _I, _P], _I),
     "vm_add_norm_fwd": (
         [_P, _I, _P, _I, _P, _P, _P, _I, _P, _I, _LL, _I, c_float, _I, _P], _I),
+    "vm_add_norm_bwd": (
+        [_P, _I, _P, _P,                          # s, dtype, weight, bias
+         _P, _I, _P,                              # dy, dtype, dres_out
+         _P, _I, _P, _I, _P, _P,                  # dx, dresidual, dweight, dbias
+         _LL, _I, c_float, _I,                    # rows, cols, eps, is_rms
+         _P, _LL, _P], _I),                       # workspace, bytes, stream
+    "vm_add_norm_bwd_workspace_bytes": ([_LL, _I], _LL),
     "vm_norm_pool_workspace_bytes": ([_I, _I, _I, _I], _LL),
     "vm_norm_pool_fwd": (
         [_P, _I, _P, _I, _LL,                     # x, residual, batch stride

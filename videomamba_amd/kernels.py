@@ -7,8 +7,10 @@ Public functions keep the call shapes the reference uses for its third-party ker
   differentiable: with grad mode on and an operand that requires grad it builds an autograd
   graph whose backward is the HIP kernel ``vm_selective_scan_bwd``
 * ``selective_state_update`` <- mamba_ssm Triton ``selective_state_update``
-* ``causal_conv1d_fn`` / ``causal_conv1d_update`` <- causal-conv1d
-* ``rms_norm_fn`` / ``layer_norm_fn`` <- mamba_ssm Triton layer norm
+* ``causal_conv1d_fn`` / ``causal_conv1d_update`` <- causal-conv1d; ``causal_conv1d_fn`` is
+  differentiable the same way (``vm_causal_conv1d_bwd``, width <= 4)
+* ``rms_norm_fn`` / ``layer_norm_fn`` <- mamba_ssm Triton layer norm, differentiable
+  (``vm_add_norm_bwd``)
 
 plus ``patch_embed`` (PatchEmbed Conv3d + positional adds).  Every function runs the HIP
 kernels of ``libvideomamba_hip.so`` on the tensors' device and current stream; CPU
@@ -413,6 +415,64 @@ def conv_raw(x, x_s, w32, b32, cs_in, csi_s, cs_out, cso_s, out, o_s, out_len, b
         _p(out), o_s[0], o_s[1], o_s[2], out_len, batch, dim, seqlen, width, int(silu), dtype,
         stream)
     _lib.check(rc, "vm_causal_conv1d_fwd")
+
+
+CONV_BWD_MAX_WIDTH = 4  # the taps vm_causal_conv1d_bwd takes (vm_conv_bwd_plan.h kCbWM)
+
+
+def _bwd_workspace(device, stream, ws_bytes: int, workspace: Optional[Tensor], what: str):
+    if not ws_bytes:
+        return None
+    if workspace is None:
+        return scratch(device, int(stream), ws_bytes)
+    if workspace.numel() < ws_bytes:
+        raise ValueError(f"{what} workspace too small: {workspace.numel()} < {ws_bytes}")
+    return workspace
+
+
+def conv_bwd_workspace_bytes(batch: int, dim: int, seqlen: int, width: int) -> int:
+    return int(_lib.load().vm_causal_conv1d_bwd_workspace_bytes(batch, dim, seqlen, width))
+
+
+def conv_bwd_raw(x, x_s, w32, b32, cs_in, csi_s, dout, do_s, dx, dx_s, dcs, dcs_s, dw, db,
+                 batch, dim, seqlen, width, silu, dtype, stream,
+                 workspace: Optional[Tensor] = None):
+    """``vm_causal_conv1d_bwd``: the gradients of :func:`conv_raw` on token-major operands
+    (unit channel stride for x / dout / dx, width <= 4).  x, w32, b32, cs_in are the forward's
+    inputs; ``dout`` is the gradient of its output.  Every gradient buffer is overwritten: dx
+    in ``dtype``, dcs (nullable, (b, d, w)), dw (d, w) and db (d; None iff b32 is None) fp32.
+    ``workspace`` (a uint8 device buffer) replaces the per-stream scratch."""
+    lib = _lib.load()
+    ws_bytes = conv_bwd_workspace_bytes(batch, dim, seqlen, width)
+    ws = _bwd_workspace(x.device, stream, ws_bytes, workspace, "conv backward")
+    rc = lib.vm_causal_conv1d_bwd(
+        _p(x), *x_s, _p(w32), _p(b32),
+        _p(cs_in), dtype_code(cs_in.dtype) if cs_in is not None else 0, *csi_s,
+        _p(dout), *do_s, _p(dx), *dx_s, _p(dcs), *dcs_s, _p(dw), _p(db),
+        batch, dim, seqlen, width, int(silu), dtype, _p(ws), ws_bytes, stream)
+    _lib.check(rc, "vm_causal_conv1d_bwd")
+
+
+def add_norm_bwd_workspace_bytes(rows: int, cols: int) -> int:
+    return int(_lib.load().vm_add_norm_bwd_workspace_bytes(rows, cols))
+
+
+def add_norm_bwd_raw(s, w32, b32, dy, dres_out, dx, dresidual, dw, db, rows, cols, eps, is_rms,
+                     stream, workspace: Optional[Tensor] = None):
+    """``vm_add_norm_bwd``: the gradients of :func:`add_norm_raw`.  ``s`` (rows, cols) is the
+    pre-norm sum the forward wrote as ``residual_out``; ``dy`` the gradient of its output,
+    ``dres_out`` (nullable, s's dtype) that of ``residual_out``; ``b32`` only says whether
+    the norm has a bias.  Overwrites dx, dresidual (nullable; the same values in its own
+    dtype), dw (cols) and db (cols; None iff b32 is None) fp32.  All buffers contiguous."""
+    lib = _lib.load()
+    ws_bytes = add_norm_bwd_workspace_bytes(rows, cols)
+    ws = _bwd_workspace(s.device, stream, ws_bytes, workspace, "add + norm backward")
+    rc = lib.vm_add_norm_bwd(
+        _p(s), dtype_code(s.dtype), _p(w32), _p(b32), _p(dy), dtype_code(dy.dtype),
+        _p(dres_out), _p(dx), dtype_code(dx.dtype), _p(dresidual),
+        dtype_code(dresidual.dtype) if dresidual is not None else 0, _p(dw), _p(db),
+        rows, cols, float(eps), int(is_rms), _p(ws), ws_bytes, stream)
+    _lib.check(rc, "vm_add_norm_bwd")
 
 
 def conv_proj_raw(xz, xz_s, cw32, cb32, cs_in, csi_s, cs_out, cso_s, wx_pad, e, wdt_pad, r,
@@ -865,13 +925,71 @@ def selective_state_update(state: Tensor, x: Tensor, dt: Tensor, A: Tensor, B: T
 
 
 # --------------------------------------------------------------------------- causal conv1d
+class _CausalConv1d(torch.autograd.Function):
+    """``conv_raw`` forward, ``conv_bwd_raw`` backward, on a token-major x with fp32 weight /
+    bias (the casts and layout changes are the caller's, as ordinary differentiable torch
+    ops).  Nothing but the inputs is saved."""
+
+    @staticmethod
+    def forward(ctx, x, w, b, cs, silu):
+        # grad mode is off in here: this is the no-grad call, same kernels, same bits
+        out = causal_conv1d_fn(x, w, b, "silu" if silu else None, conv_state=cs)
+        ctx.save_for_backward(x, w, b, cs)
+        ctx.silu = silu
+        return out
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, dout):
+        x, w, b, cs = ctx.saved_tensors
+        batch, dim, seqlen = x.shape
+        width = w.shape[1]
+        dev = x.device
+        dout = _channel_contig(dout.to(x.dtype))
+        dx = torch.empty((batch, seqlen, dim), dtype=x.dtype, device=dev).transpose(1, 2)
+        dw = torch.empty((dim, width), dtype=torch.float32, device=dev)
+        db = torch.empty((dim,), dtype=torch.float32, device=dev) if b is not None else None
+        dcs = None
+        if cs is not None and ctx.needs_input_grad[3]:
+            dcs = torch.empty((batch, dim, width), dtype=torch.float32, device=dev)
+        s2 = lambda t: (t.stride(0), t.stride(1)) if t is not None else (0, 0)  # noqa: E731
+        conv_bwd_raw(x, _tm_strides(x), w, b, cs, s2(cs), dout, _tm_strides(dout), dx,
+                     _tm_strides(dx), dcs, s2(dcs), dw, db, batch, dim, seqlen, width,
+                     ctx.silu, dtype_code(x.dtype), _stream(x))
+        return dx, dw, db, None if dcs is None else dcs.to(cs.dtype), None
+
+
+def _causal_conv1d_autograd(x, weight, bias, activation, conv_state, return_conv_state):
+    """The differentiable form of :func:`causal_conv1d_fn`: a token-major view of x, fp32
+    weight / bias and a width-contiguous state as differentiable torch ops, so every gradient
+    comes back in its input's dtype and shape, then :class:`_CausalConv1d`.  The returned conv
+    state is sliced out of ``[conv_state | x]`` by torch ops; its gradient needs no kernel."""
+    width = weight.shape[1]
+    if width > CONV_BWD_MAX_WIDTH:
+        raise NotImplementedError(f"causal_conv1d_fn backward takes width <= "
+                                  f"{CONV_BWD_MAX_WIDTH}, got {width}")
+    dtype_code(x.dtype)
+    out = _CausalConv1d.apply(_channel_contig(x), weight.float().contiguous(),
+                              None if bias is None else bias.float().contiguous(),
+                              _lastdim_contig(conv_state), activation is not None)
+    if not return_conv_state:
+        return out
+    xin = x if conv_state is None else torch.cat([conv_state, x.to(conv_state.dtype)], dim=-1)
+    if xin.shape[-1] < width:
+        xin = torch.nn.functional.pad(xin, (width - xin.shape[-1], 0))
+    return out, xin[..., xin.shape[-1] - width:].contiguous()
+
+
 def causal_conv1d_fn(x: Tensor, weight: Tensor, bias: Optional[Tensor] = None,
                      activation: Optional[str] = None, *, conv_state: Optional[Tensor] = None,
                      return_conv_state: bool = False):
     """causal-conv1d ``causal_conv1d_fn(x, weight, bias, activation)``; x: (b, d, l),
     weight: (d, w).  With ``conv_state`` (b, d, w) the conv runs over
     ``cat([conv_state, x])`` and keeps the last l outputs (``mamba_simple.py:382-390``).
-    ``return_conv_state`` also returns the last w raw inputs (new tensor)."""
+    ``return_conv_state`` also returns the last w raw inputs (new tensor).  Differentiable:
+    with grad mode on and an operand that requires grad it builds an autograd graph whose
+    backward is the HIP kernel ``vm_causal_conv1d_bwd`` (width <= 4; a channel-major x goes
+    through a token-major copy, and the output comes back in that layout)."""
     require_gpu(x, weight, bias, conv_state, what="causal_conv1d_fn")
     if activation not in (None, "silu", "swish"):
         raise NotImplementedError(f"activation {activation!r}")
@@ -879,6 +997,10 @@ def causal_conv1d_fn(x: Tensor, weight: Tensor, bias: Optional[Tensor] = None,
         weight = weight.reshape(weight.shape[0], weight.shape[-1])
     batch, dim, seqlen = x.shape
     width = weight.shape[1]
+    if torch.is_grad_enabled() and any(
+            t is not None and t.requires_grad for t in (x, weight, bias, conv_state)):
+        return _causal_conv1d_autograd(x, weight, bias, activation, conv_state,
+                                       return_conv_state)
     tm = dim > 1 and x.stride(1) == 1  # token-major view: keep the layout
     if tm:
         out = torch.empty((batch, seqlen, dim), dtype=x.dtype, device=x.device).transpose(1, 2)
@@ -921,9 +1043,93 @@ def causal_conv1d_update(x: Tensor, conv_state: Tensor, weight: Tensor,
 
 
 # --------------------------------------------------------------------------- norms
+class _AddNorm(torch.autograd.Function):
+    """``add_norm_raw`` forward, ``add_norm_bwd_raw`` backward, on contiguous (rows, cols)
+    operands with fp32 weight / bias.  The forward always writes the pre-norm sum (the
+    ``prenorm`` output, in ``rdt``); it is all the backward needs besides the weight."""
+
+    @staticmethod
+    def forward(ctx, x, res, w, b, eps, is_rms, rdt, prenorm):
+        rows, cols = x.shape
+        y = torch.empty_like(x)
+        s = torch.empty((rows, cols), dtype=rdt, device=x.device)
+        add_norm_raw(x, res, w, b, y, s, rows, cols, eps, is_rms, _stream(x))
+        ctx.save_for_backward(s, w, b)
+        ctx.eps, ctx.is_rms = eps, is_rms
+        ctx.x_dtype = x.dtype
+        ctx.res_dtype = None if res is None else res.dtype
+        ctx.set_materialize_grads(False)  # an unused return arrives as None, not as zeros
+        if not prenorm:
+            ctx.mark_non_differentiable(s)
+        return y, s
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, dy, ds_out):
+        s, w, b = ctx.saved_tensors
+        rows, cols = s.shape
+        dev = s.device
+        dy = (torch.zeros((rows, cols), dtype=ctx.x_dtype, device=dev) if dy is None
+              else dy.to(ctx.x_dtype).contiguous())
+        if ds_out is not None:
+            ds_out = ds_out.to(s.dtype).contiguous()
+        dx = torch.empty((rows, cols), dtype=ctx.x_dtype, device=dev)
+        dres = None
+        if ctx.res_dtype is not None and ctx.needs_input_grad[1]:
+            dres = torch.empty((rows, cols), dtype=ctx.res_dtype, device=dev)
+        dw = torch.empty((cols,), dtype=torch.float32, device=dev)
+        db = torch.empty((cols,), dtype=torch.float32, device=dev) if b is not None else None
+        add_norm_bwd_raw(s, w, b, dy, ds_out, dx, dres, dw, db, rows, cols, ctx.eps,
+                         ctx.is_rms, _stream(s))
+        return dx, dres, dw, db, None, None, None, None
+
+
+def _norm_autograd(x, weight, bias, residual, prenorm, residual_in_fp32, eps, is_rms):
+    """The differentiable form of :func:`_norm`: contiguous (rows, cols) views and fp32
+    weight / bias as differentiable torch ops, then :class:`_AddNorm`.  Without ``prenorm``
+    the sum is kept in the residual's dtype, or fp32 without a residual."""
+    shape = x.shape
+    cols = shape[-1]
+    dtype_code(x.dtype)
+    x2 = x.reshape(-1, cols).contiguous()
+    r2 = None if residual is None else residual.reshape(-1, cols).contiguous()
+    if residual is not None:
+        rdt = residual.dtype
+    else:
+        rdt = torch.float32 if (residual_in_fp32 or not prenorm) else x.dtype
+    y, s = _AddNorm.apply(x2, r2, weight.float().contiguous(),
+                          None if bias is None else bias.float().contiguous(),
+                          float(eps), bool(is_rms), rdt, bool(prenorm))
+    y = y.reshape(shape)
+    return (y, s.reshape(shape)) if prenorm else y
+
+
+def _norm_torch_ops(x, weight, bias, residual, prenorm, residual_in_fp32, eps, is_rms):
+    """``options.train_ops == "torch"``: the add + norm as fp32 torch ops under autograd, with
+    the kernel's rounding points (y in x's dtype, the sum in the residual's)."""
+    s = x.float() if residual is None else x.float() + residual.float()
+    if residual is not None:
+        rdt = residual.dtype
+    else:
+        rdt = torch.float32 if residual_in_fp32 else x.dtype
+    c = s if is_rms else s - s.mean(-1, keepdim=True)
+    y = c * torch.rsqrt(c.pow(2).mean(-1, keepdim=True) + eps) * weight.float()
+    if bias is not None:
+        y = y + bias.float()
+    y = y.to(x.dtype)
+    return (y, s.to(rdt)) if prenorm else y
+
+
 def _norm(x, weight, bias, residual, prenorm, residual_in_fp32, eps, is_rms, out=None,
           residual_out=None, owner=None):
     require_gpu(x, weight, bias, residual, what="rms_norm_fn/layer_norm_fn")
+    if torch.is_grad_enabled() and any(
+            t is not None and t.requires_grad for t in (x, residual, weight, bias)):
+        if out is not None or residual_out is not None:
+            raise ValueError("rms_norm_fn/layer_norm_fn: out= / residual_out= write in place, "
+                             "which has no gradient; drop them or call under torch.no_grad()")
+        fn = _norm_autograd if options.get().train_ops == "hip" else _norm_torch_ops
+        return fn(x, weight, bias, residual, prenorm, residual_in_fp32, eps, is_rms)
     shape = x.shape
     cols = shape[-1]
     x2 = x.reshape(-1, cols)
@@ -954,14 +1160,17 @@ def _norm(x, weight, bias, residual, prenorm, residual_in_fp32, eps, is_rms, out
 
 def rms_norm_fn(x: Tensor, weight: Tensor, bias: Optional[Tensor], residual: Optional[Tensor] = None,
                 prenorm: bool = False, residual_in_fp32: bool = False, eps: float = 1e-6, **_):
-    """mamba-ssm ``rms_norm_fn``: returns y, or (y, residual_out) with ``prenorm``."""
+    """mamba-ssm ``rms_norm_fn``: returns y, or (y, residual_out) with ``prenorm``.
+    Differentiable: with grad mode on and an operand that requires grad it builds an autograd
+    graph whose backward is the HIP kernel ``vm_add_norm_bwd`` (both returns carry gradient)."""
     return _norm(x, weight, bias, residual, prenorm, residual_in_fp32, eps, True)
 
 
 def layer_norm_fn(x: Tensor, weight: Tensor, bias: Optional[Tensor], residual: Optional[Tensor] = None,
                   prenorm: bool = False, residual_in_fp32: bool = False, eps: float = 1e-6,
                   is_rms_norm: bool = False, **_):
-    """mamba-ssm ``layer_norm_fn`` (LayerNorm unless ``is_rms_norm``)."""
+    """mamba-ssm ``layer_norm_fn`` (LayerNorm unless ``is_rms_norm``); differentiable as
+    :func:`rms_norm_fn`."""
     return _norm(x, weight, bias, residual, prenorm, residual_in_fp32, eps, is_rms_norm)
 
 

@@ -35,7 +35,7 @@ class RMSNorm(nn.Module):
 
 
 class DropPath(nn.Module):
-    """Stochastic depth (identity in eval mode, which is the only mode the HIP path runs)."""
+    """Stochastic depth (identity in eval mode and at rate 0)."""
 
     def __init__(self, drop_prob: float = 0.0):
         super().__init__()
@@ -75,17 +75,23 @@ _warned_grad = False
 
 
 def warn_if_grad(*tensors: Optional[Tensor]) -> None:
-    """The model-level HIP forward builds no autograd graph; say so once when autograd would
-    expect one.  (The mixer in training mode and ``selective_scan_fn`` are differentiable.)"""
+    """The inference forward builds no autograd graph; say so once when autograd would expect
+    one.  Differentiable: the model, ``Block`` and the mixer in ``.train()`` mode without
+    ``ssm_state=`` / ``inference_params``, and ``kernels.selective_scan_fn`` /
+    ``causal_conv1d_fn`` / ``rms_norm_fn`` / ``layer_norm_fn``.  Not differentiable: anything in
+    ``.eval()`` mode, forwards that carry ``ssm_state`` at model level, and the refiner."""
     global _warned_grad
     if _warned_grad or not torch.is_grad_enabled():
         return
     if any(t is not None and t.requires_grad for t in tensors):
         _warned_grad = True
-        warnings.warn("VideoMamba's model-level HIP forward is not differentiable yet: its "
-                      "outputs are computed without autograd (wrap inference in "
-                      "torch.no_grad()).  The Mamba mixer in .train() mode and "
-                      "kernels.selective_scan_fn are differentiable.", stacklevel=3)
+        warnings.warn("VideoMamba's inference forward is not differentiable: its outputs are "
+                      "computed without autograd (wrap inference in torch.no_grad()).  The "
+                      "model, Block and the Mamba mixer are differentiable in .train() mode "
+                      "without ssm_state= / inference_params, and so are "
+                      "kernels.selective_scan_fn, causal_conv1d_fn, rms_norm_fn and "
+                      "layer_norm_fn; .eval() modules, model forwards that carry ssm_state "
+                      "and the refiner are not.", stacklevel=3)
 
 
 def round_up(n: int, m: int = 8) -> int:

@@ -33,8 +33,9 @@ and keeps the state in fp32 internally.  State semantics:
 
 Training: a mixer in ``.train()`` mode called with autograd on and something that requires
 grad (and neither ``inference_params`` nor the legacy ``ssm_state=``) runs
-:meth:`Mamba._forward_train`, differentiable end to end: torch ops around the HIP scan and its
-HIP backward (vm_selective_scan_bwd).  Everything else runs the inference path above unchanged.
+:meth:`Mamba._forward_train`, differentiable end to end: torch-op projections around the HIP
+conv and scan and their HIP backwards (vm_causal_conv1d_bwd, vm_selective_scan_bwd).
+Everything else runs the inference path above unchanged.
 """
 
 from __future__ import annotations
@@ -56,6 +57,18 @@ from .gemm_tuning import tuned
 from .layers import round_up, warn_if_grad
 
 _SMALL_GEMM_K = (192, 384, 576, 768, 1152, 1536)  # vm_linear_fwd's unrolled K-step counts
+
+
+def takes_training_path(module: nn.Module, *tensors: Optional[Tensor], inference_params=None,
+                        ssm_state=None) -> bool:
+    """The one gate of the differentiable path, shared by the mixer, ``Block`` and the model so
+    the layers agree: ``module`` in ``.train()`` mode, grad mode on, neither
+    ``inference_params`` nor the legacy in-place ``ssm_state``, and an input or a parameter
+    that requires grad."""
+    return (module.training and inference_params is None and ssm_state is None
+            and torch.is_grad_enabled()
+            and (any(t is not None and t.requires_grad for t in tensors)
+                 or any(p.requires_grad for p in module.parameters())))
 
 
 def _small_gemm_ok(x: Tensor, w: Tensor, b: Optional[Tensor], out: Optional[Tensor] = None,
@@ -579,10 +592,8 @@ class Mamba(nn.Module):
             raise ValueError("state is not supported with inference_params.")
         if not hidden_states.is_cuda:
             raise RuntimeError(_CUDA_ERROR)
-        if (self.training and inference_params is None and ssm_state is None
-                and torch.is_grad_enabled()
-                and (hidden_states.requires_grad
-                     or any(p.requires_grad for p in self.parameters()))):
+        if takes_training_path(self, hidden_states, inference_params=inference_params,
+                               ssm_state=ssm_state):
             return self._forward_train(hidden_states, state, return_state)
         warn_if_grad(hidden_states, self.in_proj.weight)
         with torch.no_grad():
@@ -591,9 +602,10 @@ class Mamba(nn.Module):
     def _forward_train(self, hs: Tensor, state: Optional[Tuple[Tensor, Tensor]],
                        return_state: bool):
         """The differentiable mixer (``mamba_simple.py:333-451`` under autograd): the
-        projections and the 4-tap depthwise conv as torch ops, the scan and its gradient on
-        the HIP kernels (``K.selective_scan_fn``) over token-major views, rounding points as
-        the inference path.  With ``state`` the conv continues from ``conv_state`` and the
+        projections as torch ops (library GEMMs), the depthwise conv + SiLU and the scan with
+        their gradients on the HIP kernels (``K.causal_conv1d_fn`` for ``d_conv <= 4``,
+        ``K.selective_scan_fn``) over token-major views, rounding points as the inference
+        path.  With ``state`` the conv continues from ``conv_state`` and the
         scan from ``ssm_state``; the returned states are new tensors attached to the graph
         (the last ``d_conv`` raw conv inputs, the scan's fp32 last state)."""
         Bsz, L, _ = hs.shape
@@ -607,20 +619,25 @@ class Mamba(nn.Module):
                 self._check_state(ssm_state, N, "ssm_state", Bsz)
         xz = F.linear(hs, self.in_proj.weight, self.in_proj.bias)  # (B, L, 2D)
         x, z = xz[..., :Dm], xz[..., Dm:]
-        # causal depthwise conv over [left context | x], tap by tap in fp32
-        if conv_state is not None:
-            left = conv_state.to(x.dtype).transpose(1, 2)  # (B, W, D)
+        if W <= K.CONV_BWD_MAX_WIDTH and options.get().train_ops == "hip":
+            # causal depthwise conv + SiLU over [conv_state | x] on the HIP kernel and its HIP
+            # backward, on the token-major view of x; the state is rounded to x's dtype first
+            u = K.causal_conv1d_fn(
+                x.transpose(1, 2), self.conv1d.weight.reshape(Dm, W), self.conv1d.bias, "silu",
+                conv_state=None if conv_state is None else conv_state.to(x.dtype)
+            ).transpose(1, 2)  # (B, L, D)
+            xin = None
         else:
-            left = x.new_zeros((Bsz, W, Dm))
-        xin = torch.cat([left, x], dim=1)  # (B, W + L, D); tap k of step t is row t + 1 + k
-        w = self.conv1d.weight.reshape(Dm, W).float()
-        xf = xin.float()
-        acc = xf[:, 1:1 + L] * w[:, 0]
-        for k in range(1, W):
-            acc = acc + xf[:, 1 + k:1 + k + L] * w[:, k]
-        if self.conv1d.bias is not None:
-            acc = acc + self.conv1d.bias.float()
-        u = F.silu(acc).to(x.dtype)  # (B, L, D)
+            # wider convs (and options.train_ops == "torch"): tap by tap in fp32 torch ops
+            xin = self._conv_input(x, conv_state)  # tap k of step t is row t + 1 + k
+            w = self.conv1d.weight.reshape(Dm, W).float()
+            xf = xin.float()
+            acc = xf[:, 1:1 + L] * w[:, 0]
+            for k in range(1, W):
+                acc = acc + xf[:, 1 + k:1 + k + L] * w[:, k]
+            if self.conv1d.bias is not None:
+                acc = acc + self.conv1d.bias.float()
+            u = F.silu(acc).to(x.dtype)  # (B, L, D)
         x_dbl = F.linear(u, self.x_proj.weight, self.x_proj.bias)  # (B, L, R + 2N)
         dt = F.linear(x_dbl[..., :R], self.dt_proj.weight)  # bias added inside the scan
         A = -torch.exp(self.A_log.float())
@@ -633,8 +650,18 @@ class Mamba(nn.Module):
         if not return_state:
             return out
         cs_dtype = conv_state.dtype if conv_state is not None else hs.dtype
+        if xin is None:
+            xin = self._conv_input(x, conv_state)
         new_conv = xin[:, -W:].transpose(1, 2).to(cs_dtype)  # the last d_conv raw inputs
         return out, (new_conv, last)
+
+    def _conv_input(self, x: Tensor, conv_state: Optional[Tensor]) -> Tensor:
+        """[left context | x] as (B, d_conv + L, D) in x's dtype: the conv state, or zeros."""
+        if conv_state is not None:
+            left = conv_state.to(x.dtype).transpose(1, 2)  # (B, W, D)
+        else:
+            left = x.new_zeros((x.shape[0], self.d_conv, x.shape[2]))
+        return torch.cat([left, x], dim=1)
 
     def _forward(self, hs, inference_params, ssm_state, state, return_state):
         batch, seqlen, dm = hs.shape

@@ -95,6 +95,11 @@ documented options object; tests and sweeps change them with :func:`override`.
                      or 0, on the library.  Default 4096 (B = 1 at M-16f: 3144 rows).
     small_gemm_max_n ... and at most this many output columns (default 1024: out_proj;
                      in_proj's N = 2 * d_inner stays on the library GEMM).
+    train_ops        "hip" (default): the differentiable path runs the depthwise conv + SiLU and
+                     the add + norm on the HIP kernels and their HIP backwards
+                     (vm_causal_conv1d_bwd, vm_add_norm_bwd); "torch": the same arithmetic as
+                     torch ops under autograd (the mixer's tap loop, an fp32 add + norm) — the
+                     yardstick of scripts/bench_train_bwd.py.  The inference path never reads it.
 
 Options are process-global (not thread-local): the model is driven from one host thread,
 and the sub-batch issue threads of ``batch_stream_lock`` read the caller's options.
@@ -133,6 +138,7 @@ class Options:
     batch_stream_min_work: int = 224 * 1152
     small_gemm_rows: int = 4096
     small_gemm_max_n: int = 1024
+    train_ops: str = "hip"
 
     def validate(self) -> None:
         if self.mixer_layout not in _LAYOUTS:
@@ -147,6 +153,8 @@ class Options:
             raise ValueError(f"scan_dt_proj must be auto / on / off, got {self.scan_dt_proj!r}")
         if self.projection_gemm not in ("hip", "library"):
             raise ValueError(f"projection_gemm must be hip / library, got {self.projection_gemm!r}")
+        if self.train_ops not in ("hip", "torch"):
+            raise ValueError(f"train_ops must be hip / torch, got {self.train_ops!r}")
         if self.gemm_tuning not in _TUNING:
             raise ValueError(f"gemm_tuning must be one of {_TUNING}, got {self.gemm_tuning!r}")
 

@@ -14,6 +14,12 @@ initialisation, error types and messages: ``Block``, ``create_block``, ``PatchEm
 
 which is the same computation as calling ``Block.forward`` per layer on the unpadded
 tokens (``Block.forward`` itself is kept for callers that use blocks directly).
+
+Training: a model in ``.train()`` mode called with autograd on, something that requires grad
+and no ``ssm_state`` (``mamba_simple.takes_training_path``, the mixer's gate) runs
+``PretrainVideoMamba._encode_train`` instead: torch-op patch embed, positional adds, gather and
+pooling around ``Block.forward`` per layer, whose add + norm, conv and scan and their backwards
+are HIP kernels.  Everything else runs the inference path above unchanged.
 """
 
 from __future__ import annotations
@@ -33,7 +39,7 @@ from . import kernels as K
 from . import options
 from . import phase_lock as _phase
 from .layers import DropPath, RMSNorm, round_up, to_2tuple, trunc_normal_, warn_if_grad
-from .mamba_simple import InferenceParamsLike, Mamba
+from .mamba_simple import InferenceParamsLike, Mamba, takes_training_path
 from .streaming import (STREAMING_CONTRACT_VERSION, ForwardReturnSemantics, StateShape,
                         forward_return_semantics as _return_semantics)
 
@@ -118,13 +124,21 @@ class Block(nn.Module):
                 inference_params: Optional[InferenceParamsLike] = None,
                 use_checkpoint: bool = False, ssm_state: Optional[Tensor] = None,
                 state: Optional[Tuple[Tensor, Tensor]] = None, return_state: bool = False):
-        """hidden_states = Mixer(Norm(residual + hidden_states)).  ``use_checkpoint`` is
-        accepted for API parity (the HIP path is inference-only, nothing to recompute)."""
+        """hidden_states = Mixer(Norm(residual + hidden_states)).  In ``.train()`` mode with
+        autograd on (the mixer's gate, ``takes_training_path``) the add + norm is
+        differentiable too — fused or not, with ``DropPath`` and ``residual_in_fp32`` — so
+        gradients reach ``norm.weight``, ``hidden_states`` and ``residual``; otherwise it runs
+        without autograd as the inference path always has.  ``use_checkpoint`` is accepted for
+        API parity (activations are not recomputed)."""
         if state is not None and ssm_state is not None:
             raise ValueError("Pass either state or ssm_state, not both.")
         K.require_gpu(hidden_states, residual, what="VideoMamba")
-        with torch.no_grad():
+        if takes_training_path(self, hidden_states, residual, inference_params=inference_params,
+                               ssm_state=ssm_state):
             hidden, residual = self._add_norm(hidden_states, residual)
+        else:
+            with torch.no_grad():
+                hidden, residual = self._add_norm(hidden_states, residual)
         if state is not None:
             if return_state:
                 hidden, new_state = self.mixer(hidden, inference_params=inference_params,
@@ -647,6 +661,8 @@ class PretrainVideoMamba(nn.Module):
             raise ValueError("x must have shape [B, C, T, H, W].")
         self._validate_temporal_length(x.shape[2])
         K.require_gpu(x, what="VideoMamba")
+        if takes_training_path(self, x, ssm_state=ssm_state):
+            return self._encode_train(x, mask, temporal_pos_offset, None)[0]
         warn_if_grad(x, self.patch_embed.proj.weight)
         with torch.no_grad():
             return self._forward_features(x, mask, ssm_state, temporal_pos_offset)
@@ -880,6 +896,10 @@ class PretrainVideoMamba(nn.Module):
                                          temporal_pos_offset=temporal_pos_offset)
         self._check_pool(has_cls)
         K.require_gpu(x, what="VideoMamba")
+        if takes_training_path(self, x, ssm_state=ssm_state):
+            feats, x_pool = self._encode_train(x, mask, temporal_pos_offset,
+                                               (bool(keep_temporal), temporal_tokens, per_frame))
+            return feats[:, 1:], x_pool
         warn_if_grad(x, self.patch_embed.proj.weight)
         with torch.no_grad():
             feats, x_pool, st = self._encode(x, mask, ssm_state, temporal_pos_offset,
@@ -887,6 +907,92 @@ class PretrainVideoMamba(nn.Module):
                                                    per_frame))
         patch = feats[:, 1:] if has_cls else feats
         return (patch, x_pool) if ssm_state is None else (patch, x_pool, st)
+
+    # ------------------------------------------------------------------ training forward
+    def _encode_train(self, x, mask, temporal_pos_offset, pool):
+        """The differentiable forward (``takes_training_path``: ``.train()``, autograd on, no
+        ``ssm_state``): (features (B, N_vis, C) with the CLS row, x_pool | None), the same
+        computation with the same rounding points as :meth:`_encode`, on the unpadded tokens.
+        The patch embed is one ``F.linear`` over the video cut into patches (the proj's stride
+        equals its kernel); positional adds, CLS row, mask gather and pooling are torch ops;
+        every layer is ``Block.forward`` and the final add + norm ``K.rms_norm_fn`` /
+        ``K.layer_norm_fn``, whose hot operators and their backwards are HIP kernels."""
+        Bsz, cin, T, H, W = x.shape
+        pe = self.patch_embed
+        k = pe.tubelet_size
+        ph, pw = pe.patch_size
+        Tt = self._validate_temporal_length(T)
+        Gh, Gw = self._spatial_token_grid(H, W)
+        wt = pe.proj.weight
+        dt, C = wt.dtype, self.embed_dim
+        # crop to whole patches as the strided conv would, then one row per patch
+        v = x.to(dt)[:, :, :, :Gh * ph, :Gw * pw]
+        v = v.reshape(Bsz, cin, Tt, k, Gh, ph, Gw, pw).permute(0, 2, 4, 6, 1, 3, 5, 7)
+        tok = F.linear(v.reshape(Bsz, Tt, Gh * Gw, cin * k * ph * pw), wt.view(C, -1),
+                       pe.proj.bias)
+        spos = self._get_spatial_pos_embedding(Gh, Gw, dtype=dt, device=x.device)
+        tpos = self._get_temporal_pos_embedding(Tt, offset=temporal_pos_offset, dtype=dt,
+                                                device=x.device)
+        tok = tok + spos.unsqueeze(1)
+        tok = tok + tpos.unsqueeze(2)
+        cls = self.cls_token.to(dt).expand(Bsz, -1, -1) + self.pos_embed[:, :1].to(dt)
+        h = torch.cat([cls, tok.reshape(Bsz, Tt * Gh * Gw, C)], dim=1)
+        _, visible = self._visible_token_positions(mask, Bsz, h.shape[1], x.device,
+                                                   require_cls_visible=True)
+        if visible is not None:
+            h = h.gather(1, visible.unsqueeze(-1).expand(-1, -1, C))
+        residual = None
+        for layer in self.layers:
+            h, residual = layer(h, residual)
+        nw, nb, eps = self.norm.weight, self.norm.bias, self.norm.eps
+        norm_fn = K.rms_norm_fn if _norm_kind(self.norm) else K.layer_norm_fn
+        if self.fused_add_norm:
+            feats = norm_fn(self.drop_path(h), nw, nb, residual=residual, prenorm=False,
+                            residual_in_fp32=self.residual_in_fp32, eps=eps)
+        else:
+            residual = h if residual is None else residual + self.drop_path(h)
+            feats = norm_fn(residual.to(nw.dtype), nw, nb, eps=eps)
+        if pool is None:
+            return feats, None
+        return feats, self._pool_train(feats, visible, pool)
+
+    def _pool_train(self, feats, visible, pool):
+        """The pooling of ``videomamba.py:983-1062`` in torch ops: means over the patch tokens
+        (per frame with ``keep_temporal``; for masked input over each frame's visible
+        tokens) accumulated in fp32, the CLS add / concat of ``pool_type`` and the pool
+        LayerNorm."""
+        keep_temporal, tt, per_frame = pool
+        pn = self.pool_norm
+        mode = self.pool_type
+        cls_tok, patch = feats[:, :1], feats[:, 1:]
+        Bsz, npatch, C = patch.shape
+
+        def pool_norm(v):
+            return F.layer_norm(v, (C,), pn.weight, pn.bias, pn.eps)
+
+        if mode == "cls":
+            return pool_norm(cls_tok)
+        if npatch == 0:
+            raise ValueError("mask must keep at least one patch token visible when using "
+                             f"pool_type='{mode}'.")
+        if not keep_temporal:
+            avg = patch.float().mean(1, keepdim=True).to(patch.dtype)
+        elif visible is None:
+            avg = patch.reshape(Bsz, tt, per_frame, C).float().mean(2).to(patch.dtype)
+        else:
+            frame = torch.div(visible[:, 1:] - 1, per_frame, rounding_mode="floor")
+            onehot = (frame.unsqueeze(1) == torch.arange(tt, device=frame.device).view(1, tt, 1))
+            counts = onehot.sum(-1, keepdim=True)
+            if bool((counts == 0).any()):
+                raise ValueError("keep_temporal with masking requires at least one visible "
+                                 "patch token for each temporal slice.")
+            sums = torch.einsum("btn,bnc->btc", onehot.float(), patch.float())
+            avg = (sums / counts).to(patch.dtype)
+        if mode == "cls+avg":
+            return pool_norm(cls_tok + avg)
+        if mode == "cls_cat_avg":
+            return pool_norm(torch.cat([cls_tok, avg], dim=1))
+        return pool_norm(avg)
 
     def _check_pool(self, has_cls: bool) -> None:
         pool = self.pool_type

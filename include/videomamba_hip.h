@@ -340,10 +340,23 @@ long long vm_causal_conv1d_bwd_workspace_bytes(int batch, int dim, int seqlen, i
  * axis,  u = silu(conv1d([conv_state_in | x]))  ->  x_dbl = u @ W_x^T  ->
  * dt = x_dbl[:, :r] @ W_dt^T, rounded to bf16 at each of the three (the reference's
  * rounding points).  x: the first `dim` columns of xz rows (strides xz_sb, xz_sl; unit
- * channel stride).  u, dt: (rows, dim), x_dbl: (rows, e), all batch-contiguous
+ * channel stride).  Only the wide form (below) honours a gap between the batches' xz rows:
+ * the small-batch forms address x as one run of batch * out_len rows, so a call that
+ * would take one of them with batch > 1 and xz_sb != out_len * xz_sl returns VM_E_INVALID
+ * (and vm_conv_proj_fits answers 0).  Rows of xz with step >= seqlen, the columns past
+ * `dim` and anything outside the rows are never read into a result: they may hold NaN.
+ * u, dt: (rows, dim), x_dbl: (rows, e), all batch-contiguous
  * (sb == out_len * sl).  wx_pad: (e_pad, dim) with rows >= e zero (e_pad % 16 == 0,
  * e_pad <= 128); wdt_pad: (dim, r_pad) with columns >= r zero (r_pad 32 or 64).  Rows
- * with step >= seqlen are written as 0.  conv state as vm_causal_conv1d_fwd (width <= 4).
+ * with step >= seqlen are written as 0 in u, x_dbl and dt.
+ * Conv state (width 1 .. 4): conv_state_in (batch, dim, width), fp32 or bf16, strides
+ * (csi_sb, csi_sd, 1), nullable = zeros; conv_state_out likewise, nullable, never aliasing
+ * conv_state_in.  The state is cast to the activation dtype before the conv
+ * (mamba_simple.py:382-390): every form rounds an fp32 state's entries to bf16 where it
+ * loads them, for the conv taps and for the entries a sequence shorter than `width` carries
+ * over into conv_state_out — which so always holds bf16 values, the last `width` raw
+ * inputs of [state | x], left-padded with zeros.  (vm_causal_conv1d_fwd is not the model
+ * here: it convolves the un-rounded fp32 taps of an fp32 state under a bf16 x.)
  * dim % 64 == 0, seqlen >= 1.
  * dt == NULL skips dt_proj (conv + x_proj only; wdt_pad may then be NULL too).
  * batch <= 8 (with dt_softplus == 0, dim <= 2048, round_up(e, 4) <= 76 and out_len >= 8)
@@ -357,6 +370,8 @@ long long vm_causal_conv1d_bwd_workspace_bytes(int batch, int dim, int seqlen, i
  *   delta = softplus(float(bf16(dt)) + dt_bias[d])  (dt_bias nullable = 0), rounded to bf16
  *   — selective_scan_fn's delta_bias / delta_softplus prologue (mamba_simple.py:30-106),
  *   moved into the producer; pass delta_softplus = 0 and no delta_bias to the scan then.
+ *   Rows with step >= seqlen then hold the activation of their zero dt,
+ *   bf16(softplus(dt_bias[d])) (bf16(ln 2) without a bias): a value of the channel alone.
  */
 int vm_conv_proj_fwd(const void* xz, long long xz_sb, long long xz_sl,
                      const float* conv_weight, const float* conv_bias,
@@ -374,7 +389,8 @@ int vm_conv_proj_fwd(const void* xz, long long xz_sb, long long xz_sl,
 long long vm_conv_proj_workspace_bytes(int batch, int out_len, int dim, int e);
 
 /* ABI v10: 1 when vm_conv_proj_fwd accepts this shape's buffer extents (the small-batch forms
- * always do; the wide form needs its 31-bit buffer offsets to cover the operands, see above),
+ * need batch-contiguous xz rows at batch > 1, xz_sb == out_len * xz_sl, and nothing else;
+ * the wide form needs its 31-bit buffer offsets to cover the operands, see above),
  * 0 when it would return VM_E_INVALID for them — a caller then takes the unfused conv +
  * projection path instead.  Pure host code. */
 int vm_conv_proj_fits(int batch, int out_len, int seqlen, int dim, int e, int r_pad,
@@ -394,7 +410,9 @@ int vm_conv_proj_fits(int batch, int out_len, int seqlen, int dim, int e, int r_
  * hn: (batch * out_len, k) bf16, row stride ldh; w_in: (2 dim, k) bf16, row stride ldw;
  * k in {192, 384, 576, 768, 1152, 1536}; batch <= 8, out_len >= 56 (even), dim % 128 == 0
  * and <= 2048, R + 2N <= 76 (e_pad <= 80), width <= 4; conv weights / state, wx_pad,
- * wdt_pad as vm_conv_proj_fwd.  Rows with step >= seqlen get u = 0.  `workspace`:
+ * wdt_pad as vm_conv_proj_fwd (an fp32 conv state is rounded to bf16 where it is loaded,
+ * as there).  Rows with step >= seqlen get u = x_dbl = dt = 0; z is the GEMM of every row
+ * of hn, whatever its step.  `workspace`:
  * vm_in_proj_conv_proj_workspace_bytes() bytes (the x_dbl partials).
  * vm_in_proj_conv_proj_fits: 1 when the shape is accepted (pure host code).
  */
@@ -419,7 +437,8 @@ int vm_in_proj_conv_proj_fits(int k, int batch, int out_len, int dim, int e, int
  * x: the first `dim` rows of xz, row stride x_sd, columns = batch * out_len tokens (batch b's
  * steps at columns b*out_len + t, unit stride).  u, dt: (dim, batch*out_len) row strides
  * u_sd / dt_sd; x_dbl: (e, batch*out_len) row stride xd_sd.  Columns with t >= seqlen are
- * written as 0.  wx_pad / wdt_pad / conv weights and state as vm_conv_proj_fwd.
+ * written as 0.  wx_pad / wdt_pad / conv weights and state as vm_conv_proj_fwd (an fp32
+ * conv state is rounded to bf16 where it is loaded, as there).
  * The x_proj reduction over channels runs in a fixed split order (fp32 partials in
  * `workspace`, vm_conv_proj_cm_workspace_bytes() bytes), so every token's outputs are
  * independent of the sequence length and batch (chunked == full-sequence, bitwise).

@@ -50,16 +50,21 @@ static void check_token_major(const ConvProjPlanIn& in, const ConvProjPlan& pl, 
       (!in.has_cs_in ||
        ((in.batch - 1) * in.csi_sb + (in.dim - 1) * in.csi_sd + in.width) * cs_es <= 0x7fffff00ll) &&
       64 * in.u_sl * 2 <= 0x7fffff00ll;
-  const ConvProjForm want = fused ? ConvProjForm::kFused
+  // the small forms read x as one run of ntok rows: a gap between the batches' xz rows
+  // (which only the wide form honours) is refused
+  const bool gap = small && in.batch > 1 && in.xz_sb != in.out_len * in.xz_sl;
+  const ConvProjForm want = gap ? ConvProjForm::kNone
+                            : fused ? ConvProjForm::kFused
                             : small ? ConvProjForm::kSplitK
                             : wide_ok ? ConvProjForm::kWide : ConvProjForm::kNone;
   CHECK(pl.form == want);
   CHECK((pl.why == ConvProjWhy::kOk) == (pl.form != ConvProjForm::kNone));
-  if (pl.form == ConvProjForm::kNone) CHECK(pl.why == ConvProjWhy::kWideOffsets);
+  if (pl.form == ConvProjForm::kNone)
+    CHECK(pl.why == (gap ? ConvProjWhy::kSmallXzGap : ConvProjWhy::kWideOffsets));
   ++seen[static_cast<int>(pl.form)];
   // ---- the size query answers for every batch <= 8, the entry asks the small forms only
   CHECK(pl.ws_query == (in.batch <= 8 ? sk_bytes : 0));
-  CHECK(pl.ws_need == (small ? sk_bytes : 0));
+  CHECK(pl.ws_need == (small && !gap ? sk_bytes : 0));
   if (pl.form == ConvProjForm::kNone) return;
   CHECK(pl.ntok == ntok && pl.ep == ep && pl.NB == in.e_pad / 16);
   CHECK(pl.main.lds <= kLdsPerCu && pl.reduce.lds == 0 && pl.state.lds == 0);
@@ -192,6 +197,12 @@ int main() {
     in.entry = ConvProjEntry::kConvProj;
     check_token_major(in, plan_conv_proj(in), seen);
     ++plans;
+    if (flags == 0 || flags == 7) {  // the same shape with 8 rows between the batches' xz
+      in.xz_sb += 8 * in.xz_sl;
+      check_token_major(in, plan_conv_proj(in), seen);
+      ++plans;
+      in.xz_sb -= 8 * in.xz_sl;
+    }
     // ---- vm_conv_proj_cm_*
     in.layout = ConvProjLayout::kChannelMajor;
     if (flags < 8) {

@@ -539,12 +539,13 @@ def _conv_proj_tm_call(lib, **over):
     a = dict(D=1152, E=68, Ep=80, R=36, Rp=64, L=3137, Lp=3144, batch=2, width=4,
              dtype=_lib.VM_DTYPE_BF16, spd=0, xz=_fake(0), cw=_fake(1), cs_in=None, cs_out=None,
              wx=_fake(3), wdt=_fake(4), u=_fake(5), xdbl=_fake(6), dt=_fake(7), ws=_fake(8),
-             ws_bytes=1 << 40, u_sb=None)
+             ws_bytes=1 << 40, u_sb=None, xz_sb=None)
     a.update(over)
     s = SimpleNamespace(**a)
     u_sb = s.Lp * s.D if s.u_sb is None else s.u_sb
+    xz_sb = s.Lp * 2 * s.D if s.xz_sb is None else s.xz_sb
     return lib.vm_conv_proj_fwd(
-        s.xz, s.Lp * 2 * s.D, 2 * s.D, s.cw, _fake(2),
+        s.xz, xz_sb, 2 * s.D, s.cw, _fake(2),
         s.cs_in, 0, s.D * 4, 4, s.cs_out, 0, s.D * 4, 4,
         s.wx, s.E, s.Ep, s.wdt, s.R, s.Rp,
         s.u, u_sb, s.D, s.xdbl, s.Lp * s.E, s.E, s.dt, s.Lp * s.D, s.D,
@@ -656,6 +657,11 @@ _CONV_PROJ_REFUSALS = [
     (_conv_proj_tm_call, dict(batch=0, ws=None), 0, None),
     (_conv_proj_cm_call, dict(batch=0), 0, None),
     (_conv_proj_cm_call, dict(batch=0, ws=None), 0, None),
+    # batch-contiguity of xz: the small forms address x as one run of token rows (kept last:
+    # the rows above keep the indices they were recorded under)
+    (_conv_proj_tm_call, dict(xz_sb=(3144 + 8) * 2 * 1152), -1,
+     b"vm_conv_proj_fwd: the small-batch forms need batch-contiguous xz rows "
+     b"(xz_sb == out_len * xz_sl), got xz_sb %d" % ((3144 + 8) * 2 * 1152)),
 ]
 
 
@@ -663,7 +669,9 @@ _CONV_PROJ_REFUSALS = [
 def test_conv_proj_entries_refuse_as_recorded(row):
     """The three mixer-middle entries refuse on the host, before any HIP call, with the
     return code and message they had before the plan (fake pointers, never dereferenced):
-    null pointer, shape, alignment, batch-contiguity, aliasing, workspace, 31-bit offsets."""
+    null pointer, shape, alignment, batch-contiguity, aliasing, workspace, 31-bit offsets.
+    The gapped-xz row is the one refusal added since: a small form with batch > 1 and
+    xz_sb != out_len * xz_sl."""
     call, over, rc, text = _CONV_PROJ_REFUSALS[row]
     lib = _lib.load()
     assert call(lib, **over) == rc

@@ -731,6 +731,7 @@ def test_patch_embed_kernels_agree_bitwise(T, kt, C):
     _close(one[:, 1:], ref, 2e-2)
 
 
+# (All five conv_proj forms against a float64 reference: test_gpu_mixer_mid_matrix.py.)
 def test_conv_proj_without_dt_matches_with_dt():
     """vm_conv_proj_fwd with dt == NULL (conv + x_proj only) writes the same u and x_dbl
     bits as the full kernel; the full kernel's dt equals x_dbl[:, :R] @ W_dt^T from the

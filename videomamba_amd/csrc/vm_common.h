@@ -46,6 +46,13 @@ __device__ __forceinline__ float load_dyn(const void* p, long long i, int dtype)
   if (dtype == VM_DTYPE_BF16) return to_f32(reinterpret_cast<const bf16_t*>(p)[i]);
   return reinterpret_cast<const float*>(p)[i];
 }
+// A conv-state tap as the bf16 mixer middle reads it: the state is cast to the activation
+// dtype before the conv (mamba_simple.py:382-390), so an fp32 state is rounded to bf16 where
+// it is loaded.  A bf16 state is unchanged.
+__device__ __forceinline__ float load_cs_bf16(const void* p, long long i, int dtype) {
+  if (dtype == VM_DTYPE_BF16) return to_f32(reinterpret_cast<const bf16_t*>(p)[i]);
+  return round_to<bf16_t>(reinterpret_cast<const float*>(p)[i]);
+}
 __device__ __forceinline__ void store_dyn(void* p, long long i, int dtype, float v) {
   if (dtype == VM_DTYPE_BF16) reinterpret_cast<bf16_t*>(p)[i] = from_f32<bf16_t>(v);
   else reinterpret_cast<float*>(p)[i] = v;

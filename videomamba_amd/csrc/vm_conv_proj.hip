@@ -440,8 +440,8 @@ __global__ __launch_bounds__(256) void conv_state_out_kernel(const ConvProjParam
     const int te = p.seqlen - p.width + s;
     float val = 0.0f;
     if (te >= 0) val = to_f32(xrow[(long long)te * p.xz_sl + c]);
-    else if (p.csi) val = load_dyn(p.csi, b * p.csi_sb + (long long)c * p.csi_sd + p.width + te,
-                                   p.csi_dtype);
+    else if (p.csi) val = load_cs_bf16(p.csi, b * p.csi_sb + (long long)c * p.csi_sd + p.width + te,
+                                       p.csi_dtype);
     store_dyn(p.cso, b * p.cso_sb + (long long)c * p.cso_sd + s, p.cso_dtype, val);
   }
 }
@@ -521,6 +521,12 @@ extern "C" int vm_conv_proj_fwd(const void* xz, long long xz_sb, long long xz_sl
   if (pl.why == ConvProjWhy::kWideOffsets) {
     vmhost::set_error("vm_conv_proj_fwd: batch > %d needs a sequence of xz under 1 GiB "
                       "(31-bit buffer offsets)", kSkMaxBatch);
+    return VM_E_INVALID;
+  }
+  if (pl.why == ConvProjWhy::kSmallXzGap) {
+    vmhost::set_error("vm_conv_proj_fwd: the small-batch forms need batch-contiguous xz rows "
+                      "(xz_sb == out_len * xz_sl), got xz_sb %lld for out_len %d, xz_sl %lld",
+                      xz_sb, out_len, xz_sl);
     return VM_E_INVALID;
   }
   if (pl.small()) {

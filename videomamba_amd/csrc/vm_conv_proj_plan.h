@@ -110,6 +110,7 @@ enum class ConvProjWhy {
   kWideOffsets,  // the wide form's 31-bit buffer offsets do not cover the operands
   kInProjShape,  // outside the in_proj form's shapes, or its 31-bit extents
   kCmShape,      // channel-major: dim % 64 != 0 or a non-positive size
+  kSmallXzGap,   // a small form with batch > 1 whose xz rows are not batch-contiguous
 };
 
 struct ConvProjPlanIn {
@@ -230,6 +231,12 @@ inline ConvProjPlan plan_conv_proj(const ConvProjPlanIn& in) {
   const bool small = in.batch <= kSkMaxBatch && !in.dt_softplus && in.dim <= kSkMaxSpl * kSkCh &&
                      pl.ep <= kSkMaxEp && in.r_pad <= 80 && in.out_len >= kSkMinLen;
   if (small) {
+    // the small forms address x as one run of ntok rows (x + token * xz_sl); only the wide
+    // form reads xz_sb, so a gap between the batches' rows is refused, not misread
+    if (in.batch > 1 && in.xz_sb != static_cast<long long>(in.out_len) * in.xz_sl) {
+      pl.why = ConvProjWhy::kSmallXzGap;
+      return pl;
+    }
     pl.nsplit = pl.NSPL = sk_splits(in.dim);
     pl.ws_need = sk_bytes;
     // one fused launch where it applies, else the two split-K launches; the fused form's

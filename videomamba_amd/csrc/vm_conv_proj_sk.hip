@@ -120,7 +120,7 @@ __global__ __launch_bounds__(256) void conv_xproj_cm_kernel(const ConvProjCmPara
               float v = 0.0f;
               if (j >= 0) v = to_f32(xr[i - (W - 1) + k]);
               else if (p.csi && tok < p.ntok)
-                v = load_dyn(p.csi, b * p.csi_sb + (long long)c * p.csi_sd + W + j, p.csi_dtype);
+                v = load_cs_bf16(p.csi, b * p.csi_sb + (long long)c * p.csi_sd + W + j, p.csi_dtype);
               a = fmaf(w[k], v, a);
             }
           }
@@ -262,8 +262,8 @@ __global__ __launch_bounds__(256) void conv_state_cm_kernel(const ConvProjCmPara
     const int te = p.seqlen - p.width + s;
     float val = 0.0f;
     if (te >= 0) val = to_f32(p.x[(long long)c * p.x_sd + (long long)b * p.lp + te]);
-    else if (p.csi) val = load_dyn(p.csi, b * p.csi_sb + (long long)c * p.csi_sd + p.width + te,
-                                   p.csi_dtype);
+    else if (p.csi) val = load_cs_bf16(p.csi, b * p.csi_sb + (long long)c * p.csi_sd + p.width + te,
+                                       p.csi_dtype);
     store_dyn(p.cso, b * p.cso_sb + (long long)c * p.cso_sd + s, p.cso_dtype, val);
   }
 }
@@ -337,8 +337,8 @@ __global__ __launch_bounds__(256) void conv_xproj_tm_kernel(const SkTmParams q) 
     const int tap = W - 1 - m;  // state column of step -(m + 1)
     cv[k] = 0.0f;
     if (bb < nbs && ch < nch && tap >= 0)
-      cv[k] = load_dyn(p.csi, (b_lo + bb) * p.csi_sb + (long long)(c0 + ch) * p.csi_sd + tap,
-                       p.csi_dtype);
+      cv[k] = load_cs_bf16(p.csi, (b_lo + bb) * p.csi_sb + (long long)(c0 + ch) * p.csi_sd + tap,
+                           p.csi_dtype);
   }
 #pragma unroll
   for (int k = 0; k < kSkCsLoads; ++k) {
@@ -370,7 +370,7 @@ __global__ __launch_bounds__(256) void conv_xproj_tm_kernel(const SkTmParams q) 
         if (te >= 0)
           v = to_f32(sX[(kCmHalo + b * p.out_len + te - tok0) * kTmPitch + tid]);
         else if (p.csi)
-          v = load_dyn(p.csi, b * p.csi_sb + (long long)ch * p.csi_sd + W + te, p.csi_dtype);
+          v = load_cs_bf16(p.csi, b * p.csi_sb + (long long)ch * p.csi_sd + W + te, p.csi_dtype);
         store_dyn(p.cso, b * p.cso_sb + (long long)ch * p.cso_sd + s, p.cso_dtype, v);
       }
     }
@@ -696,8 +696,8 @@ __global__ __launch_bounds__(64 * kFuMaxSpl) void conv_proj_fused_kernel(const S
                                                        static_cast<int>(span), 0x00020000);
     auto tap = [&](long long idx, bool ok) {
       const int off = opaque(ok ? static_cast<int>(idx * es) : kOut);
-      if constexpr (CS32)
-        return __uint_as_float(__builtin_amdgcn_raw_buffer_load_b32(csr, off, 0, 0));
+      if constexpr (CS32)  // rounded to bf16 as load_cs_bf16 (an out-of-range 0 stays 0)
+        return round_to<bf16_t>(__uint_as_float(__builtin_amdgcn_raw_buffer_load_b32(csr, off, 0, 0)));
       else
         return __uint_as_float(static_cast<uint32_t>(__builtin_amdgcn_raw_buffer_load_b16(csr, off, 0, 0)) << 16);
     };
@@ -904,8 +904,8 @@ __global__ __launch_bounds__(64 * kFuMaxSpl) void conv_proj_fused_kernel(const S
             vh = __uint_as_float(v & 0xffff0000u);
           } else if (p.csi) {
             const long long base = (long long)be * p.csi_sb + (long long)c * p.csi_sd + W + te;
-            vl = load_dyn(p.csi, base, p.csi_dtype);
-            vh = load_dyn(p.csi, base + p.csi_sd, p.csi_dtype);
+            vl = load_cs_bf16(p.csi, base, p.csi_dtype);
+            vh = load_cs_bf16(p.csi, base + p.csi_sd, p.csi_dtype);
           }
           const long long ob = (long long)be * p.cso_sb + (long long)c * p.cso_sd + s2;
           store_dyn(p.cso, ob, p.cso_dtype, vl);

@@ -190,8 +190,8 @@ __global__ __launch_bounds__(512) void inproj_conv_kernel(const InConvParams q) 
         const int tap = W - 1 - m;  // state column of step -(m + 1)
         cv[k] = 0.0f;
         if (bb < nbs && tap >= 0)
-          cv[k] = load_dyn(p.csi, (b_lo + bb) * p.csi_sb + (long long)(c0 + ch) * p.csi_sd + tap,
-                           p.csi_dtype);
+          cv[k] = load_cs_bf16(p.csi, (b_lo + bb) * p.csi_sb + (long long)(c0 + ch) * p.csi_sd + tap,
+                               p.csi_dtype);
       }
     }
   };
@@ -271,7 +271,7 @@ __global__ __launch_bounds__(512) void inproj_conv_kernel(const InConvParams q) 
         if (te >= 0)
           v = to_f32(sO[(b * p.out_len + te - m0) * kIcPitch + tid]);
         else if (p.csi)
-          v = load_dyn(p.csi, b * p.csi_sb + (long long)ch * p.csi_sd + W + te, p.csi_dtype);
+          v = load_cs_bf16(p.csi, b * p.csi_sb + (long long)ch * p.csi_sd + W + te, p.csi_dtype);
         store_dyn(p.cso, b * p.cso_sb + (long long)ch * p.cso_sd + s, p.cso_dtype, v);
       }
     }

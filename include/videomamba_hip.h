@@ -555,8 +555,9 @@ int vm_pool_finish_fwd(const void* workspace, int batch, int groups, int group_r
 /*
  * out (m, n) = x (m, k) @ w (n, k)^T (+ bias (n), fp32, nullable): bf16 operands, fp32
  * accumulation, rows K-contiguous with leading dimensions ldx / ldw / ldo (elements).
- * n, k and the leading dimensions multiples of 8, 16-byte aligned operands.  Each output
- * row is computed in the same order for every m (sequence-length independent).
+ * k in {192, 384, 576, 768, 1152, 1536} (the unrolled K-step counts the kernels are built
+ * for), n and the leading dimensions multiples of 8, 16-byte aligned operands, w under 2 GB.
+ * Each output row is computed in the same order for every m (sequence-length independent).
  */
 int vm_linear_fwd(const void* x, long long ldx, const void* w, long long ldw,
                   const float* bias, void* out, long long ldo, int m, int n, int k, int dtype,

@@ -253,24 +253,24 @@ VARIANTS = {
     "ldma_old": [("vm_gemm.hip", "constexpr bool kLinearDma = true;", "constexpr bool kLinearDma = false;")],
     # LDS-DMA GEMM tile / depth alternatives: 128x128 with three stage buffers (one
     # workgroup per CU); narrow outputs on 128x64 tiles with three buffers
-    "ldma3": [("vm_gemm.hip", "  if (p.n >= 1024) VM_LDMA_TILE(128, 128, 2, 4)",
-               "  if (p.n >= 1024) VM_LDMA_TILE(128, 128, 3, 2)")],
-    "ldma_o64": [("vm_gemm.hip", "  else VM_LDMA_TILE(128, 64, 3, 4)",
-                  "  else VM_LDMA_TILE(64, 64, 3, 2)")],
-    "ldma_o2": [("vm_gemm.hip", "  else VM_LDMA_TILE(128, 64, 3, 4)",
-                 "  else VM_LDMA_TILE(64, 64, 2, 2)")],
+    "ldma3": [("vm_gemm_plan.h", "constexpr DmaTile kDmaWide{128, 128, 2, 4};",
+               "constexpr DmaTile kDmaWide{128, 128, 3, 2};")],
+    "ldma_o64": [("vm_gemm_plan.h", "constexpr DmaTile kDmaNarrow{128, 64, 3, 4};",
+                  "constexpr DmaTile kDmaNarrow{64, 64, 3, 2};")],
+    "ldma_o2": [("vm_gemm_plan.h", "constexpr DmaTile kDmaNarrow{128, 64, 3, 4};",
+                 "constexpr DmaTile kDmaNarrow{64, 64, 2, 2};")],
     # LDS-DMA GEMM tile alternatives for in_proj (N >= 1024) and out_proj at B = 1
-    "ldma_i128x64": [("vm_gemm.hip", "  if (p.n >= 1024) VM_LDMA_TILE(128, 128, 2, 4)",
-                      "  if (p.n >= 1024) VM_LDMA_TILE(128, 64, 3, 2)")],
+    "ldma_i128x64": [("vm_gemm_plan.h", "constexpr DmaTile kDmaWide{128, 128, 2, 4};",
+                      "constexpr DmaTile kDmaWide{128, 64, 3, 2};")],
     # wide conv_proj occupancy probe: LDS padded so 2 (cp_occ2) workgroups fit per CU instead of 3
     "cp_occ2": [("vm_conv_proj.hip", "dim3(pl.main.block), pl.main.lds, st, p);",
                  "dim3(pl.main.block), pl.main.lds + 30000, st, p);")],
     # final norm + pooling through the dtype-generic rows kernel only
     "np_generic": [("vm_norm.hip", "constexpr bool kPoolFast = true;", "constexpr bool kPoolFast = false;")],
-    "ldma16_i128x128": [("vm_gemm.hip", "  if (p.n >= 1024) VM_LDMA_TILE(128, 128, 2, 4)",
-                         "  if (p.n >= 1024) VM_LDMA_TILE(128, 128, 2, 8)")],
-    "ldma8_i64x128": [("vm_gemm.hip", "  if (p.n >= 1024) VM_LDMA_TILE(128, 128, 2, 4)",
-                       "  if (p.n >= 1024) VM_LDMA_TILE(64, 128, 2, 4)")],
+    "ldma16_i128x128": [("vm_gemm_plan.h", "constexpr DmaTile kDmaWide{128, 128, 2, 4};",
+                         "constexpr DmaTile kDmaWide{128, 128, 2, 8};")],
+    "ldma8_i64x128": [("vm_gemm_plan.h", "constexpr DmaTile kDmaWide{128, 128, 2, 4};",
+                       "constexpr DmaTile kDmaWide{64, 128, 2, 4};")],
     # fused small-batch conv_proj pricing (results wrong): W_x fragments from an out-of-range
     # offset (no traffic) / no x_proj MFMA / no u stores
     "cf_nowx": [("vm_conv_proj_sk.hip",
@@ -287,36 +287,36 @@ VARIANTS = {
                 "  const int tok0 = [] { const int nwg = gridDim.x, h = blockIdx.x, x = h & 7, q = nwg >> 3, r = nwg & 7;"
                 " return ((x < r ? x * (q + 1) : r * (q + 1) + (x - r) * q) + (h >> 3)) * kFuTok; }();")],
     # eight-wave (4 x 2) forms at one workgroup per CU (round 4)
-    "ldma8_i256x128": [("vm_gemm.hip", "  if (p.n >= 1024) VM_LDMA_TILE(128, 128, 2, 4)",
-                        "  if (p.n >= 1024) VM_LDMA_TILE(256, 128, 2, 4)")],
-    "ldma8_i256x128b3": [("vm_gemm.hip", "  if (p.n >= 1024) VM_LDMA_TILE(128, 128, 2, 4)",
-                          "  if (p.n >= 1024) VM_LDMA_TILE(256, 128, 3, 4)")],
-    "ldma8_i128x128": [("vm_gemm.hip", "  if (p.n >= 1024) VM_LDMA_TILE(128, 128, 2, 4)",
-                        "  if (p.n >= 1024) VM_LDMA_TILE(128, 128, 2, 4)")],
-    "ldma8_i128x128b3": [("vm_gemm.hip", "  if (p.n >= 1024) VM_LDMA_TILE(128, 128, 2, 4)",
-                          "  if (p.n >= 1024) VM_LDMA_TILE(128, 128, 3, 4)")],
-    "ldma8_i128x256": [("vm_gemm.hip", "  if (p.n >= 1024) VM_LDMA_TILE(128, 128, 2, 4)",
-                        "  if (p.n >= 1024) VM_LDMA_TILE(128, 256, 2, 4)")],
-    "ldma16_i256x128": [("vm_gemm.hip", "  if (p.n >= 1024) VM_LDMA_TILE(128, 128, 2, 4)",
-                         "  if (p.n >= 1024) VM_LDMA_TILE(256, 128, 2, 8)")],
-    "ldma16_i128x128b3": [("vm_gemm.hip", "  if (p.n >= 1024) VM_LDMA_TILE(128, 128, 2, 4)",
-                           "  if (p.n >= 1024) VM_LDMA_TILE(128, 128, 3, 8)")],
-    "ldma16_o128x64": [("vm_gemm.hip", "  else VM_LDMA_TILE(128, 64, 3, 4)",
-                        "  else VM_LDMA_TILE(128, 64, 3, 8)")],
-    "ldma8_o128x64b2": [("vm_gemm.hip", "  else VM_LDMA_TILE(128, 64, 3, 4)",
-                         "  else VM_LDMA_TILE(128, 64, 2, 4)")],
-    "ldma8_o128x64": [("vm_gemm.hip", "  else VM_LDMA_TILE(128, 64, 3, 4)",
-                       "  else VM_LDMA_TILE(128, 64, 3, 4)")],
-    "ldma8_o128x64b4": [("vm_gemm.hip", "  else VM_LDMA_TILE(128, 64, 3, 4)",
-                         "  else VM_LDMA_TILE(128, 64, 4, 4)")],
-    "ldma_i256x128": [("vm_gemm.hip", "  if (p.n >= 1024) VM_LDMA_TILE(128, 128, 2, 4)",
-                       "  if (p.n >= 1024) VM_LDMA_TILE(256, 128, 2, 2)")],
-    "ldma_i128x256": [("vm_gemm.hip", "  if (p.n >= 1024) VM_LDMA_TILE(128, 128, 2, 4)",
-                       "  if (p.n >= 1024) VM_LDMA_TILE(128, 256, 2, 2)")],
-    "ldma_i64x128": [("vm_gemm.hip", "  if (p.n >= 1024) VM_LDMA_TILE(128, 128, 2, 4)",
-                      "  if (p.n >= 1024) VM_LDMA_TILE(64, 128, 3, 2)")],
-    "ldma_o64n4": [("vm_gemm.hip", "  else VM_LDMA_TILE(128, 64, 3, 4)",
-                    "  else VM_LDMA_TILE(64, 64, 4, 2)")],
+    "ldma8_i256x128": [("vm_gemm_plan.h", "constexpr DmaTile kDmaWide{128, 128, 2, 4};",
+                        "constexpr DmaTile kDmaWide{256, 128, 2, 4};")],
+    "ldma8_i256x128b3": [("vm_gemm_plan.h", "constexpr DmaTile kDmaWide{128, 128, 2, 4};",
+                          "constexpr DmaTile kDmaWide{256, 128, 3, 4};")],
+    "ldma8_i128x128": [("vm_gemm_plan.h", "constexpr DmaTile kDmaWide{128, 128, 2, 4};",
+                        "constexpr DmaTile kDmaWide{128, 128, 2, 4};")],
+    "ldma8_i128x128b3": [("vm_gemm_plan.h", "constexpr DmaTile kDmaWide{128, 128, 2, 4};",
+                          "constexpr DmaTile kDmaWide{128, 128, 3, 4};")],
+    "ldma8_i128x256": [("vm_gemm_plan.h", "constexpr DmaTile kDmaWide{128, 128, 2, 4};",
+                        "constexpr DmaTile kDmaWide{128, 256, 2, 4};")],
+    "ldma16_i256x128": [("vm_gemm_plan.h", "constexpr DmaTile kDmaWide{128, 128, 2, 4};",
+                         "constexpr DmaTile kDmaWide{256, 128, 2, 8};")],
+    "ldma16_i128x128b3": [("vm_gemm_plan.h", "constexpr DmaTile kDmaWide{128, 128, 2, 4};",
+                           "constexpr DmaTile kDmaWide{128, 128, 3, 8};")],
+    "ldma16_o128x64": [("vm_gemm_plan.h", "constexpr DmaTile kDmaNarrow{128, 64, 3, 4};",
+                        "constexpr DmaTile kDmaNarrow{128, 64, 3, 8};")],
+    "ldma8_o128x64b2": [("vm_gemm_plan.h", "constexpr DmaTile kDmaNarrow{128, 64, 3, 4};",
+                         "constexpr DmaTile kDmaNarrow{128, 64, 2, 4};")],
+    "ldma8_o128x64": [("vm_gemm_plan.h", "constexpr DmaTile kDmaNarrow{128, 64, 3, 4};",
+                       "constexpr DmaTile kDmaNarrow{128, 64, 3, 4};")],
+    "ldma8_o128x64b4": [("vm_gemm_plan.h", "constexpr DmaTile kDmaNarrow{128, 64, 3, 4};",
+                         "constexpr DmaTile kDmaNarrow{128, 64, 4, 4};")],
+    "ldma_i256x128": [("vm_gemm_plan.h", "constexpr DmaTile kDmaWide{128, 128, 2, 4};",
+                       "constexpr DmaTile kDmaWide{256, 128, 2, 2};")],
+    "ldma_i128x256": [("vm_gemm_plan.h", "constexpr DmaTile kDmaWide{128, 128, 2, 4};",
+                       "constexpr DmaTile kDmaWide{128, 256, 2, 2};")],
+    "ldma_i64x128": [("vm_gemm_plan.h", "constexpr DmaTile kDmaWide{128, 128, 2, 4};",
+                      "constexpr DmaTile kDmaWide{64, 128, 3, 2};")],
+    "ldma_o64n4": [("vm_gemm_plan.h", "constexpr DmaTile kDmaNarrow{128, 64, 3, 4};",
+                    "constexpr DmaTile kDmaNarrow{64, 64, 4, 2};")],
     # one-launch chunked scan: the preceding blocks' flags polled one after another by
     # thread 0 (the round-2 form) instead of in parallel by wave 0
     "poll_serial": [("vm_scan_seq.hip", "        for (int j = lane; j < blk; j += 64)",

@@ -709,6 +709,84 @@ def test_linear_rejects_unsupported_k_before_launch():
         assert rc == -1 and b"k = " in lib.vm_last_error(), k
 
 
+def _gemm_refusal_table():
+    return json.load(open(os.path.join(ROOT, "tests", "golden", "gemm_refusals.json")))
+
+
+def _gemm_refusal_calls():
+    """The recorder's own argument marshalling (tests/golden/gen_gemm_refusals.py)."""
+    import importlib.util
+    spec = importlib.util.spec_from_file_location(
+        "gen_gemm_refusals", os.path.join(ROOT, "tests", "golden", "gen_gemm_refusals.py"))
+    gen = importlib.util.module_from_spec(spec)
+    spec.loader.exec_module(gen)
+    return gen
+
+
+def test_gemm_entries_answer_as_recorded():
+    """vm_linear_fwd_form, vm_linear_add_norm_fwd and vm_linear_add_norm_counter_bytes against
+    tests/golden/gemm_refusals.json: return code and full vm_last_error() text as recorded
+    from the library built at the commit the file names, before the host side was folded into
+    vm_gemm_plan.h.  Every call has m <= 0, so none can launch on any device (m == 0 returns
+    VM_OK only after the form, shape and K tests; m == -1 is refused by the shape block), and
+    the made-up pointers are never dereferenced.  Every row must come back unchanged."""
+    lib = _lib.load()
+    gen = _gemm_refusal_calls()
+    table = _gemm_refusal_table()
+    assert table["linear_columns"] == gen.LINEAR_COLUMNS + ["rc", "error"]
+    assert table["add_norm_columns"] == gen.ADD_NORM_COLUMNS + ["rc", "error"]
+    rows = 0
+    bad = []
+    for name, call in (("linear_rows", gen.call_linear), ("add_norm_rows", gen.call_add_norm)):
+        for row in table[name]:
+            assert row[table[name.replace("_rows", "_columns")].index("m")] <= 0
+            rc = call(lib, row[:-2])
+            got = [rc, "" if rc == 0 else lib.vm_last_error().decode()]
+            if got != row[-2:]:
+                bad.append((name, row, got))
+            rows += 1
+    for m, want in table["counter_bytes_rows"]:
+        if lib.vm_linear_add_norm_counter_bytes(m) != want:
+            bad.append(("counter_bytes", m, want))
+        rows += 1
+    assert rows >= 150
+    assert len(table["counter_bytes_rows"]) >= 12
+    assert not bad, bad[:5]
+
+
+def test_gemm_plan_check_program_passes_under_sanitizers(tmp_path):
+    """tests/host/gemm_plan_check.cpp walks vm_gemm_plan.h::plan_linear and
+    plan_linear_add_norm over shapes x leading dimensions x forms x alignments x CU counts and
+    exits non-zero on any plan whose form differs from the rules written out there, whose
+    template selectors are not instantiated, whose grid or tiles do not cover m x n, whose LDS
+    does not fit, whose buffer extents reach 2^31 bytes or whose counter bytes are off.  Built
+    as a program of its own under ASan + UBSan, as conv_proj_plan_check.cpp is."""
+    rocm_clang = "/opt/rocm/llvm/bin/clang++"
+    cxx = [rocm_clang] if os.path.exists(rocm_clang) else \
+        [shutil.which("g++") or "g++", "-static-libasan", "-static-libubsan"]
+    exe = str(tmp_path / "gemm_plan_check")
+    subprocess.run(cxx + ["-std=c++17", "-O1", "-g", "-fsanitize=address,undefined",
+                    "-fno-sanitize-recover=all", "-I", os.path.join(ROOT, "videomamba_amd", "csrc"),
+                    os.path.join(ROOT, "tests", "host", "gemm_plan_check.cpp"), "-o", exe],
+                   check=True, timeout=120)
+    run = subprocess.run([exe], capture_output=True, text=True, timeout=120)
+    assert run.returncode == 0, run.stdout + run.stderr
+    assert " 0 failures" in run.stdout
+
+
+def test_small_gemm_k_mirrors_the_library():
+    """mamba_simple._SMALL_GEMM_K (the Python routing's copy of the K set) is the set of k,
+    over every multiple of 64 up to 2048, that an m == 0 vm_linear_fwd accepts (m == 0: no
+    launch on any device; the K test comes before it)."""
+    from videomamba_amd.mamba_simple import _SMALL_GEMM_K
+    lib = _lib.load()
+    fake = lambda i: ctypes.c_void_p((i + 1) << 20)  # noqa: E731  never dereferenced
+    accepted = [k for k in range(64, 2048 + 64, 64)
+                if lib.vm_linear_fwd(fake(0), k, fake(1), k, None, fake(2), 64, 0, 64, k,
+                                     _lib.VM_DTYPE_BF16, None) == 0]
+    assert tuple(accepted) == tuple(_SMALL_GEMM_K)
+
+
 def test_sync_rearm_clears_only_the_error_word():
     """re-arming a sync buffer after a reported timeout zeroes word 0 (the error
     word) only; the epoch (word 1) keeps growing so stale granules of earlier launches never

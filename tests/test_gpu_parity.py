@@ -1100,6 +1100,40 @@ def test_linear_add_norm_bitwise_equals_linear_then_add_norm(m, n, k):
         assert torch.equal(hn, hn_ref)
     cnt = K.counter_buffer(x.device, torch.cuda.current_stream().cuda_stream, 0)
     assert not cnt.any()
+    if m == 12552:
+        # 891 workgroups are past any CU count and 150 tiles below the persistent threshold:
+        # the two separate launches, which refuse a column-sliced hn
+        wide = torch.empty(m, 2 * n, device=DEV, dtype=torch.bfloat16)
+        with pytest.raises(RuntimeError, match="contiguous"):
+            K.linear_add_norm(x, w, res0.clone(), nw, 1e-5, wide[:, :n])
+
+
+@pytest.mark.parametrize("k", [192, 384, 576, 768, 1152, 1536])
+def test_linear_add_norm_every_k_bitwise_equals_linear_then_add_norm(k):
+    """Every K-step count through the one-launch form's dispatch switch: m = 300, n = 192 is
+    a 3 x 3 grid of 128 x 64 tiles (9 workgroups: co-resident on any device, ragged last row
+    tile).  h, the fp32 residual and the normalised rows are bit-equal to vm_linear_fwd
+    followed by vm_add_norm_fwd, and the hand-off counters come back zeroed."""
+    m, n = 300, 192
+    torch.manual_seed(k)
+    x = torch.randn(m, k, device=DEV).to(torch.bfloat16)
+    w = (torch.randn(n, k, device=DEV) / k ** 0.5).to(torch.bfloat16)
+    res0 = torch.randn(m, n, device=DEV)
+    nw = torch.rand(n, device=DEV) + 0.5
+    h_ref = K.linear(x, w)
+    res_ref = res0.clone()
+    hn_ref = torch.empty(m, n, device=DEV, dtype=torch.bfloat16)
+    K.add_norm_raw(h_ref, res_ref, nw, None, hn_ref, res_ref, m, n, 1e-5, True,
+                   torch.cuda.current_stream().cuda_stream)
+    res = res0.clone()
+    hn = torch.zeros(m, n, device=DEV, dtype=torch.bfloat16)
+    h = K.linear_add_norm(x, w, res, nw, 1e-5, hn)
+    torch.cuda.synchronize()
+    assert torch.equal(h, h_ref)
+    assert torch.equal(res, res_ref)
+    assert torch.equal(hn, hn_ref)
+    cnt = K.counter_buffer(x.device, torch.cuda.current_stream().cuda_stream, 0)
+    assert not cnt.any()
 
 
 @pytest.mark.parametrize("m,n,k", [(3144, 576, 1152), (1576, 192, 384), (777, 576, 1152)])
@@ -1192,6 +1226,31 @@ def test_persistent_linear_bitwise_equals_dma_tiles(m, n, k):
     assert ((y_tile[:m].float() - ref).abs() <= ref.abs() * 2.0 ** -8 + 1e-3).all()
 
 
+@pytest.mark.parametrize("n", [192, 1024])
+@pytest.mark.parametrize("k", [192, 384, 576, 768, 1152, 1536])
+def test_linear_every_k_through_every_form(k, n):
+    """Every K-step count through the four dispatch switches of vm_linear_fwd_form: n = 192
+    takes the 128 x 64 LDS-DMA tiles and the 256 x 192 persistent tiles, n = 1024 the
+    128 x 128 and 256 x 256 ones; m = 300 leaves a ragged second 256-row tile and a ragged
+    third 128-row tile.  The persistent form is bit-equal to the LDS-DMA form, neither writes
+    a row past m of a padded output, and both are within one bf16 rounding of the fp32
+    product (the bound of the tests around this one)."""
+    m = 300
+    torch.manual_seed(k + n)
+    x = torch.randn(m, k, device=DEV).to(torch.bfloat16)
+    w = (torch.randn(n, k, device=DEV) * k ** -0.5).to(torch.bfloat16)
+    ref = x.float() @ w.float().t()
+    outs = {}
+    for form in ("dma", "persistent"):
+        out = torch.full((m + 5, n), 7.0, device=DEV, dtype=torch.bfloat16)
+        K.linear(x, w, out=out[:m], form=form)
+        torch.cuda.synchronize()
+        assert (out[m:] == 7.0).all(), form  # nothing past row m
+        assert ((out[:m].float() - ref).abs() <= ref.abs() * 2.0 ** -8 + 1e-3).all(), form
+        outs[form] = out[:m]
+    assert torch.equal(outs["persistent"], outs["dma"])
+
+
 @pytest.mark.parametrize("m,n,k", [(20000, 2304, 576), (20000, 576, 1152)])
 def test_persistent_linear_rows_independent_of_m_and_output_stride(m, n, k):
     """Chunk invariance of the projections at chip-filling batches: a row's
@@ -1237,6 +1296,9 @@ def test_persistent_linear_past_2gb_matches_slices_and_fp32(m, n, k, past):
     row_bytes = (n if past == "out" else k) * 2
     assert m * row_bytes > 2 ** 31
     y = K.linear(x, w)  # the auto choice: the persistent form (the only one past 2 GB)
+    if past == "x":  # the LDS-DMA form addresses x through one 31-bit buffer
+        with pytest.raises(RuntimeError, match="past 2 GB"):
+            K.linear(x, w, form="dma")
     assert torch.equal(K.linear(x, w, form="persistent"), y)
     edge = 2 ** 31 // row_bytes
     for lo, hi in [(0, 700), (edge - 300, edge + 300), ((edge // 256) * 256 - 5, (edge // 256) * 256 + 261),

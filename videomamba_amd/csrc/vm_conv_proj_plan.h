@@ -9,6 +9,8 @@
 
 #include <cstddef>
 
+#include "vm_gemm_plan.h"
+
 namespace vm {
 
 // ---------------------------------------------------------------- shared constants
@@ -39,7 +41,7 @@ constexpr int kFuXRows = 20;    // x rows staged per wave (tok0 - 3 .. tok0 + 16
 constexpr int kFuMinLen = 24;   // at most one sequence start in tok0 - 2 .. tok0 + 15
 constexpr int kFuMaxEpad = 80;  // wider x_proj outputs exceed the 576-thread register budget
 
-constexpr int kIcRow = 128;     // in_proj form: bytes per staged K row (64 bf16)
+constexpr int kIcRow = kGemmRow;  // in_proj form: bytes per staged K row (64 bf16)
 constexpr int kIcOut = 112;     // x output rows per tile
 constexpr int kIcHalo = 16;     // rows above them computed for the conv
 constexpr int kIcPitch = 136;   // bf16 pitch of the LDS x / u tile
@@ -186,13 +188,8 @@ inline ConvProjPlan plan_conv_proj(const ConvProjPlanIn& in) {
 
   if (in.entry == ConvProjEntry::kInProjConvProj) {
     pl.ws_query = pl.ws_need = sk_bytes;
-    bool k_ok = in.k % 64 == 0;
-    switch (in.k / 64) {  // the K-step counts inproj_conv_kernel is instantiated for
-      case 3: case 6: case 9: case 12: case 18: case 24: break;
-      default: k_ok = false;
-    }
-    const bool ok =
-        k_ok && in.batch >= 1 && in.batch <= kSkMaxBatch && in.dim % 128 == 0 &&
+    const bool ok =  // inproj_conv_kernel is instantiated for the projection GEMM's K steps
+        gemm_k_ok(in.k) && in.batch >= 1 && in.batch <= kSkMaxBatch && in.dim % 128 == 0 &&
         in.dim <= kSkMaxSpl * kSkCh && in.out_len >= kIcMinLen && in.e_pad <= kFuMaxEpad &&
         in.e_pad % 16 == 0 && pl.ep <= kSkMaxEp && (!in.want_dt || in.r_pad <= 64) &&
         in.width >= 1 && in.width <= 4 &&
@@ -205,7 +202,7 @@ inline ConvProjPlan plan_conv_proj(const ConvProjPlanIn& in) {
     }
     pl.form = ConvProjForm::kInProj;
     pl.nsplit = pl.NSPL = in.dim / kSkCh;
-    pl.NK = in.k / 64;
+    pl.NK = in.k / kGemmBK;
     pl.nxr = tiles_of(kIcOut);
     pl.nzr = tiles_of(128);
     pl.tiles = pl.nxr;

@@ -10,7 +10,7 @@
 // not depend on the sequence length (chunked == full).  vm_linear_add_norm_fwd runs the same
 // kernel with the next block's residual add + RMSNorm as a second phase (NORM).
 
-#include "vm_common.h"
+#include "vm_gemm.h"
 
 namespace vm {
 
@@ -46,8 +46,6 @@ __device__ __forceinline__ float lin_wave_sum(float v) {
   return v;
 }
 
-constexpr int kLinBK = 64;  // K step
-
 // ---------------------------------------------------------------- LDS-DMA pipelined form
 // Per-row K order: 64-wide steps, two 16x16x32 MFMAs per step in k order (the persistent
 // kernel's too, so every output row is bit-identical whatever the tile shape), with the
@@ -63,8 +61,6 @@ constexpr int kLinBK = 64;  // K step
 // DMA writes lane-linear).  Rows past m / n read as zero (buffer range) and are never
 // stored.  Workgroups are renumbered so each XCD owns a contiguous run of M tiles (their x
 // rows enter one L2 once; W is read by every XCD).
-constexpr int kDmaRow = 128;  // bytes per staged row
-
 __device__ __forceinline__ int dma_slot(int row, int chunk) { return chunk ^ ((row >> 1) & 7); }
 // s_waitcnt vmcnt(N) lgkmcnt(0) (expcnt left at its maximum)
 template <int N>
@@ -80,7 +76,7 @@ __device__ __forceinline__ void dma_wait_vm_lgkm0() {
 // the host launches it only when the whole grid is co-resident (grid <= CUs).
 template <int BM, int BN, int NK, int NBUF, int NWM = 2, bool NORM = false>
 __global__ __launch_bounds__(128 * NWM) void linear_dma_kernel(const LinParams p, const NormTail q) {
-  constexpr int R = kDmaRow;
+  constexpr int R = kGemmRow;
   constexpr int NW = 2 * NWM;     // waves
   constexpr int NT = 64 * NW;     // threads
   constexpr int STAGE = (BM + BN) * R;
@@ -278,7 +274,7 @@ __global__ __launch_bounds__(128 * NWM) void linear_dma_kernel(const LinParams p
     // The whole grid is co-resident (host check), so a poll never waits on an undispatched
     // producer; it is bounded anyway: a timeout sets the error word and makes the rows NaN.
     unsigned* err = q.cnt;
-    unsigned* tcnt = q.cnt + 16;
+    unsigned* tcnt = q.cnt + kCntHead;
     const int nmt = (p.m + BM - 1) / BM;
     unsigned* ccnt = tcnt + nmt;
     // (the flag lives in the dynamic LDS, free after the stores: a second __shared__ object
@@ -399,55 +395,101 @@ __global__ __launch_bounds__(128 * NWM) void linear_dma_kernel(const LinParams p
   }
 }
 
-// Tile choice for the pipelined form (row bits do not depend on it), measured at the B = 1
-// chunk shapes (scripts/diag/variant_linear.py): wide outputs (in_proj, N = 2 * d_inner)
-// on 128 x 128 tiles with two stage buffers (64 KB: two workgroups per CU; 14.1 us against
-// 17.6 for the register ring, three buffers 16.3), eight waves each since round 4 (four per
-// SIMD with the second workgroup: 13.2 against 14.3-14.7 us, B = 2 21.9 against 22.9;
-// 256 x 128 / 128 x 256 tiles at one workgroup per CU, 8 or 16 waves, 14.2-14.3 us;
-// profiles/r04x_linear_waves.jsonl); narrow ones (out_proj, N = d_model) on 128 x 64
-// tiles with three buffers (72 KB; 9.1 against 11.3 us), eight waves since round 4 (B = 1
-// the same 9.4 us, B = 2 12.5-13.0 against 13.2-13.4; profiles/r04z_out_proj_waves.jsonl).
-#define VM_LDMA_TILE(BMV, BNV, NBV, NWMV)                                                     \
-  {                                                                                           \
-    const dim3 grid((p.m + BMV - 1) / BMV, (p.n + BNV - 1) / BNV);                            \
-    const size_t lds = static_cast<size_t>(NBV) * (BMV + BNV) * kDmaRow;                      \
-    switch (p.k / kLinBK) {                                                                   \
-      VM_LDMA_K(BMV, BNV, NBV, NWMV, 3) VM_LDMA_K(BMV, BNV, NBV, NWMV, 6)                     \
-      VM_LDMA_K(BMV, BNV, NBV, NWMV, 9) VM_LDMA_K(BMV, BNV, NBV, NWMV, 12)                    \
-      VM_LDMA_K(BMV, BNV, NBV, NWMV, 18) VM_LDMA_K(BMV, BNV, NBV, NWMV, 24)                   \
-      default: break;                                                                         \
-    }                                                                                         \
-  }
-#define VM_LDMA_K(BMV, BNV, NBV, NWMV, NKV)                                                    \
-  case NKV:                                                                                    \
-    hipLaunchKernelGGL((linear_dma_kernel<BMV, BNV, NKV, NBV, NWMV>), grid, dim3(128 * NWMV), \
-                       lds, s, p, NormTail{});                                                 \
-    break;
-static void linear_dma_launch(const LinParams& p, hipStream_t s) {
-  if (p.n >= 1024) VM_LDMA_TILE(128, 128, 2, 4)
-  else VM_LDMA_TILE(128, 64, 3, 4)
-}
+// Tile choice for the pipelined form (row bits do not depend on it; the shapes are kDmaWide
+// and kDmaNarrow in vm_gemm_plan.h), measured at the B = 1 chunk shapes
+// (scripts/diag/variant_linear.py): wide outputs (in_proj, N = 2 * d_inner) on 128 x 128
+// tiles with two stage buffers (64 KB: two workgroups per CU; 14.1 us against 17.6 for the
+// register ring, three buffers 16.3), eight waves each since round 4 (four per SIMD with the
+// second workgroup: 13.2 against 14.3-14.7 us, B = 2 21.9 against 22.9; 256 x 128 /
+// 128 x 256 tiles at one workgroup per CU, 8 or 16 waves, 14.2-14.3 us;
+// profiles/r04x_linear_waves.jsonl); narrow ones (out_proj, N = d_model) on 128 x 64 tiles
+// with three buffers (72 KB; 9.1 against 11.3 us), eight waves since round 4 (B = 1 the same
+// 9.4 us, B = 2 12.5-13.0 against 13.2-13.4; profiles/r04z_out_proj_waves.jsonl).
+template <int BM, int BN, int NBUF, int NWM, bool NORM>
+static int linear_dma_launch_tile(const LinParams& p, const NormTail& q, const GemmPlan& pl,
+                                  hipStream_t s) {
+  const dim3 grid(pl.gx, pl.gy), block(pl.block);
+  switch (pl.NK) {
+#define VM_LDMA_K(NKV)                                                                          \
+  case NKV:                                                                                     \
+    hipLaunchKernelGGL((linear_dma_kernel<BM, BN, NKV, NBUF, NWM, NORM>), grid, block, pl.lds, \
+                       s, p, q);                                                                \
+    return VM_OK;
+    VM_GEMM_NK_LIST(VM_LDMA_K)
 #undef VM_LDMA_K
+  }
+  return gemm_no_instance("linear_dma_kernel", pl);
+}
+#define VM_LDMA_TILE(T, NORM) \
+  linear_dma_launch_tile<T.bm, T.bn, T.nbuf, T.nwm, NORM>(p, q, pl, s)
+
+int linear_dma_launch(const GemmArgs& a, const GemmPlan& pl, hipStream_t s) {
+  LinParams p{};
+  p.x = a.x; p.ldx = a.ldx; p.w = a.w; p.ldw = a.ldw;
+  p.bias = a.bias; p.out = a.out; p.ldo = a.ldo;
+  p.m = a.m; p.n = a.n; p.k = a.k;
+  NormTail q{};
+  switch (pl.form) {
+    case GemmForm::kDma128x128: return VM_LDMA_TILE(kDmaWide, false);
+    case GemmForm::kDma128x64: return VM_LDMA_TILE(kDmaNarrow, false);
+    case GemmForm::kDmaNorm:
+      q.res = a.res; q.ldr = a.ldr; q.w = a.nw; q.hn = a.hn; q.ldh = a.ldh;
+      q.eps = a.eps; q.cnt = a.cnt;
+      return VM_LDMA_TILE(kDmaNormTile, true);
+    default: return gemm_no_instance("linear_dma_kernel", pl);
+  }
+}
 #undef VM_LDMA_TILE
 
-// The persistent 256-row tile kernel (vm_gemm_tile.hip): bit-identical rows, used once the
-// tile count fills every CU several times over.
-int gemm_tile_bn(int m, int n, int k, long long ldx, long long ldw, long long ldo);
-long long gemm_tile_count(int m, int n, int bn);
-void gemm_tile_launch(const bf16_t* x, long long ldx, const bf16_t* w, long long ldw,
-                      bf16_t* out, long long ldo, int m, int n, int k, int bn, int workgroups,
-                      hipStream_t s);
-bool gemm_tile_norm_ok(int n, int k, int bn);
-void gemm_tile_norm_launch(const bf16_t* x, long long ldx, const bf16_t* w, long long ldw,
-                           bf16_t* out, long long ldo, float* res, long long ldr, const float* nw,
-                           float eps, bf16_t* hn, long long ldh, unsigned* cnt, int m, int n,
-                           int k, int workgroups, hipStream_t s);
-// the persistent kernel runs from 1.5 tiles per CU (twice the tile count >= 3 x CUs): C5's
-// in_proj (12,544 rows, 441 tiles) 41.9 -> ~35 us, the C5 chunk 8.55 -> 8.26 ms
-constexpr int kTileMinPerCU2 = 3;
+int gemm_no_instance(const char* kernel, const GemmPlan& pl) {
+  vmhost::set_error("%s: no instance for plan form %d, NK %d, NC %d (a bug in vm_gemm_plan.h "
+                    "or its launch switch)", kernel, static_cast<int>(pl.form), pl.NK, pl.NC);
+  return VM_E_INVALID;
+}
 
-using vmhost::device_cus;
+// Every refusal of the two entries: one return code and one text each.
+static int gemm_refuse(GemmWhy why, const GemmPlanIn& in) {
+  switch (why) {
+    case GemmWhy::kOk: return VM_OK;
+    case GemmWhy::kFormArg:
+      vmhost::set_error("vm_linear_fwd_form: form %d (0 auto, 1 LDS-DMA tiles, 2 persistent)",
+                        in.form);
+      break;
+    case GemmWhy::kShape:
+      vmhost::set_error("vm_linear_fwd: bf16 only; k a multiple of 64; n and the leading "
+                        "dimensions multiples of 8; 16-byte aligned operands, w under 2 GB");
+      break;
+    case GemmWhy::kK:
+      vmhost::set_error("vm_linear_fwd: k = %d (supported: 192, 384, 576, 768, 1152, 1536)", in.k);
+      break;
+    case GemmWhy::kTileShape:
+      vmhost::set_error("vm_linear_fwd_form: the persistent form needs no bias, n a multiple of "
+                        "192 or 256 and 256-row ranges under 2 GB");
+      break;
+    case GemmWhy::kTileCus:
+      vmhost::set_error("vm_linear_fwd_form: the persistent form needs the launch device's CU "
+                        "count (query failed or < 8 CUs)");
+      break;
+    case GemmWhy::kXPast2GB:
+      vmhost::set_error("vm_linear_fwd: x past 2 GB needs the persistent form (no bias, n a "
+                        "multiple of 192 or 256)");
+      break;
+    case GemmWhy::kNormShape:
+      vmhost::set_error("vm_linear_add_norm_fwd: bf16 x / w / h / hn, fp32 residual and weight; "
+                        "k a multiple of 64, n a multiple of 8 and <= 1024, 16-byte aligned "
+                        "rows, w under 2 GB, vm_linear_add_norm_counter_bytes(m) zeroed counters");
+      break;
+    case GemmWhy::kNormK:
+      vmhost::set_error("vm_linear_add_norm_fwd: k = %d (supported: 192, 384, 576, 768, 1152, "
+                        "1536)", in.k);
+      break;
+    case GemmWhy::kNormStrides:
+      vmhost::set_error("vm_linear_add_norm_fwd: a grid past the CU count runs the separate "
+                        "kernels, which need contiguous h / residual / hn rows");
+      break;
+  }
+  return VM_E_INVALID;
+}
 
 }  // namespace vm
 
@@ -466,64 +508,29 @@ extern "C" int vm_linear_fwd_form(const void* x, long long ldx, const void* w, l
     vmhost::set_error("vm_linear_fwd: null required pointer");
     return VM_E_INVALID;
   }
-  if (form < 0 || form > 2) {
-    vmhost::set_error("vm_linear_fwd_form: form %d (0 auto, 1 LDS-DMA tiles, 2 persistent)", form);
-    return VM_E_INVALID;
-  }
-  if (dtype != VM_DTYPE_BF16 || m < 0 || n < 1 || k < kLinBK || n % 8 || k % kLinBK ||
-      ldx < k || ldw < k || ldo < n || ldx % 8 || ldw % 8 || ldo % 8 || !vmhost::aligned16(x) ||
-      !vmhost::aligned16(w) || !vmhost::aligned16(out) || (long long)n * ldw * 2 >= (1ll << 31)) {
-    vmhost::set_error("vm_linear_fwd: bf16 only; k a multiple of 64; n and the leading "
-                      "dimensions multiples of 8; 16-byte aligned operands, w under 2 GB");
-    return VM_E_INVALID;
-  }
-  switch (k / kLinBK) {  // the unrolled K-step counts both kernel forms are built for
-    case 3: case 6: case 9: case 12: case 18: case 24: break;
-    default:
-      vmhost::set_error("vm_linear_fwd: k = %d (supported: 192, 384, 576, 768, 1152, 1536)", k);
-      return VM_E_INVALID;
-  }
-  if (m == 0) return VM_OK;
-  LinParams p{};
-  p.x = static_cast<const bf16_t*>(x); p.ldx = ldx;
-  p.w = static_cast<const bf16_t*>(w); p.ldw = ldw;
-  p.bias = bias; p.out = static_cast<bf16_t*>(out); p.ldo = ldo;
-  p.m = m; p.n = n; p.k = k;
   hipStream_t s = static_cast<hipStream_t>(stream);
-  const int bn = bias ? 0 : gemm_tile_bn(m, n, k, ldx, ldw, ldo);
-  if (form == 2 && !bn) {
-    vmhost::set_error("vm_linear_fwd_form: the persistent form needs no bias, n a multiple of "
-                      "192 or 256 and 256-row ranges under 2 GB");
-    return VM_E_INVALID;
+  GemmPlanIn in{};
+  in.m = m; in.n = n; in.k = k; in.ldx = ldx; in.ldw = ldw; in.ldo = ldo;
+  in.has_bias = bias != nullptr; in.bf16 = dtype == VM_DTYPE_BF16; in.form = form;
+  in.x_al = vmhost::aligned16(x); in.w_al = vmhost::aligned16(w); in.o_al = vmhost::aligned16(out);
+  GemmPlan pl = plan_linear(in);
+  if (pl.reads_cus) {  // only a call that may launch queries the device
+    in.cus = vmhost::device_cus(s);
+    pl = plan_linear(in);
   }
-  if (form != 1 && bn) {
-    const int wgs = device_cus(s) / 8 * 8;  // persistent workgroups: whole XCD runs
-    if (form == 2 && wgs < 8) {
-      vmhost::set_error("vm_linear_fwd_form: the persistent form needs the launch device's CU "
-                        "count (query failed or < 8 CUs)");
-      return VM_E_INVALID;
-    }
-    if (wgs >= 8 && (form == 2 || 2 * gemm_tile_count(m, n, bn) >=
-                                      static_cast<long long>(kTileMinPerCU2) * wgs)) {
-      gemm_tile_launch(p.x, ldx, p.w, ldw, p.out, ldo, m, n, k, bn, wgs, s);
-      return vmhost::launch_status("vm_linear_fwd");
-    }
-  }
-  // the LDS-DMA and register-ring forms address x through one buffer (31-bit offsets)
-  if ((long long)m * ldx * 2 >= (1ll << 31)) {
-    vmhost::set_error("vm_linear_fwd: x past 2 GB needs the persistent form (no bias, n a "
-                      "multiple of 192 or 256)");
-    return VM_E_INVALID;
-  }
-  linear_dma_launch(p, s);
-  return vmhost::launch_status("vm_linear_fwd");
+  if (pl.form == GemmForm::kNone) return gemm_refuse(pl.why, in);
+  if (pl.form == GemmForm::kEmpty) return VM_OK;
+  GemmArgs a{};
+  a.x = static_cast<const bf16_t*>(x); a.ldx = ldx;
+  a.w = static_cast<const bf16_t*>(w); a.ldw = ldw;
+  a.bias = bias; a.out = static_cast<bf16_t*>(out); a.ldo = ldo;
+  a.m = m; a.n = n; a.k = k;
+  const bool tile = pl.form == GemmForm::kTile256 || pl.form == GemmForm::kTile192;
+  const int rc = tile ? gemm_tile_launch(a, pl, s) : linear_dma_launch(a, pl, s);
+  return rc != VM_OK ? rc : vmhost::launch_status("vm_linear_fwd");
 }
 
-// Counter buffer of vm_linear_add_norm_fwd: an error word (+ pad) and two counters per
-// 128-row tile (producers, consumers).
-extern "C" long long vm_linear_add_norm_counter_bytes(int m) {
-  return m <= 0 ? 0 : static_cast<long long>(16 + 2 * ((m + 127) / 128)) * sizeof(unsigned);
-}
+extern "C" long long vm_linear_add_norm_counter_bytes(int m) { return gemm_counter_bytes(m); }
 
 extern "C" int vm_linear_add_norm_fwd(const void* x, long long ldx, const void* w, long long ldw,
                                       void* h, long long ldo, float* residual, long long ldr,
@@ -534,75 +541,36 @@ extern "C" int vm_linear_add_norm_fwd(const void* x, long long ldx, const void* 
     vmhost::set_error("vm_linear_add_norm_fwd: null required pointer");
     return VM_E_INVALID;
   }
-  if (m < 0 || n < 4 || n > 1024 || n % 8 || k < kLinBK || k % kLinBK || ldx < k || ldw < k ||
-      ldo < n || ldr < n || ldh < n || ldx % 8 || ldw % 8 || ldo % 8 || ldr % 4 || ldh % 4 ||
-      !vmhost::aligned16(x) || !vmhost::aligned16(w) || !vmhost::aligned16(h) ||
-      !vmhost::aligned16(residual) || !vmhost::aligned16(norm_weight) || !vmhost::aligned16(hn) ||
-      (long long)n * ldw * 2 >= (1ll << 31) || counter_bytes < vm_linear_add_norm_counter_bytes(m)) {
-    vmhost::set_error("vm_linear_add_norm_fwd: bf16 x / w / h / hn, fp32 residual and weight; "
-                      "k a multiple of 64, n a multiple of 8 and <= 1024, 16-byte aligned "
-                      "rows, w under 2 GB, vm_linear_add_norm_counter_bytes(m) zeroed counters");
-    return VM_E_INVALID;
-  }
-  switch (k / kLinBK) {
-    case 3: case 6: case 9: case 12: case 18: case 24: break;
-    default:
-      vmhost::set_error("vm_linear_add_norm_fwd: k = %d (supported: 192, 384, 576, 768, 1152, "
-                        "1536)", k);
-      return VM_E_INVALID;
-  }
-  if (m == 0) return VM_OK;
   hipStream_t s = static_cast<hipStream_t>(stream);
-  // one launch when the whole 128 x 64-tile grid is co-resident at one workgroup per CU
-  constexpr int BM = 128, BN = 64;
-  const long long nwg = static_cast<long long>((m + BM - 1) / BM) * ((n + BN - 1) / BN);
-  const int cus = device_cus(s);
-  if (cus > 0 && nwg <= cus) {
-    LinParams p{};
-    p.x = static_cast<const bf16_t*>(x); p.ldx = ldx;
-    p.w = static_cast<const bf16_t*>(w); p.ldw = ldw;
-    p.bias = nullptr; p.out = static_cast<bf16_t*>(h); p.ldo = ldo;
-    p.m = m; p.n = n; p.k = k;
-    NormTail q{};
-    q.res = residual; q.ldr = ldr; q.w = norm_weight; q.hn = static_cast<bf16_t*>(hn); q.ldh = ldh;
-    q.eps = eps; q.cnt = static_cast<unsigned*>(counters);
-    const dim3 grid((m + BM - 1) / BM, (n + BN - 1) / BN);
-    // 3 stage buffers = 72 KB; 96 KB requested so a CU holds one workgroup (the validated
-    // one-per-CU form of the hand-off)
-    const size_t lds = 96 * 1024;
-    switch (k / kLinBK) {
-#define VM_LN(NKV)                                                                               \
-  case NKV:                                                                                      \
-    hipLaunchKernelGGL((linear_dma_kernel<BM, BN, NKV, 3, 4, true>), grid, dim3(512), lds, s, p, q); \
-    break;
-      VM_LN(3) VM_LN(6) VM_LN(9) VM_LN(12) VM_LN(18) VM_LN(24)
-#undef VM_LN
-      default: break;
-    }
-    return vmhost::launch_status("vm_linear_add_norm_fwd");
+  GemmPlanIn in{};
+  in.m = m; in.n = n; in.k = k; in.ldx = ldx; in.ldw = ldw; in.ldo = ldo;
+  in.bf16 = true;
+  in.x_al = vmhost::aligned16(x); in.w_al = vmhost::aligned16(w); in.o_al = vmhost::aligned16(h);
+  in.ldr = ldr; in.ldh = ldh;
+  in.r_al = vmhost::aligned16(residual); in.nw_al = vmhost::aligned16(norm_weight);
+  in.hn_al = vmhost::aligned16(hn);
+  in.counter_bytes = counter_bytes;
+  GemmPlan pl = plan_linear_add_norm(in);
+  if (pl.reads_cus) {  // only a call that may launch queries the device
+    in.cus = vmhost::device_cus(s);
+    pl = plan_linear_add_norm(in);
   }
-  // chip-filling row counts: the persistent tile GEMM with the norm pass per 256-row block
-  // (vm_gemm_tile.hip, NORM), where vm_linear_fwd_form would pick the persistent form
-  {
-    const int bn = gemm_tile_bn(m, n, k, ldx, ldw, ldo);
-    const int wgs = cus / 8 * 8;
-    if (bn && gemm_tile_norm_ok(n, k, bn) && wgs >= 8 &&
-        2 * gemm_tile_count(m, n, bn) >= static_cast<long long>(kTileMinPerCU2) * wgs) {
-      gemm_tile_norm_launch(static_cast<const bf16_t*>(x), ldx, static_cast<const bf16_t*>(w), ldw,
-                            static_cast<bf16_t*>(h), ldo, residual, ldr, norm_weight, eps,
-                            static_cast<bf16_t*>(hn), ldh, static_cast<unsigned*>(counters), m, n,
-                            k, wgs, s);
-      return vmhost::launch_status("vm_linear_add_norm_fwd");
-    }
+  if (pl.form == GemmForm::kNone) return gemm_refuse(pl.why, in);
+  if (pl.form == GemmForm::kEmpty) return VM_OK;
+  if (pl.form == GemmForm::kTwoLaunch) {
+    int rc = vm_linear_fwd_form(x, ldx, w, ldw, nullptr, h, ldo, m, n, k, VM_DTYPE_BF16, 0, stream);
+    if (rc != VM_OK) return rc;
+    return vm_add_norm_fwd(h, VM_DTYPE_BF16, residual, VM_DTYPE_F32, norm_weight, nullptr, hn,
+                           VM_DTYPE_BF16, residual, VM_DTYPE_F32, m, n, eps, 1, stream);
   }
-  // otherwise the two launches it replaces (the same kernels: bit-identical either way)
-  if (ldo != n || ldr != n || ldh != n) {
-    vmhost::set_error("vm_linear_add_norm_fwd: a grid past the CU count runs the separate "
-                      "kernels, which need contiguous h / residual / hn rows");
-    return VM_E_INVALID;
-  }
-  int rc = vm_linear_fwd_form(x, ldx, w, ldw, nullptr, h, ldo, m, n, k, VM_DTYPE_BF16, 0, stream);
-  if (rc != VM_OK) return rc;
-  return vm_add_norm_fwd(h, VM_DTYPE_BF16, residual, VM_DTYPE_F32, norm_weight, nullptr, hn,
-                         VM_DTYPE_BF16, residual, VM_DTYPE_F32, m, n, eps, 1, stream);
+  GemmArgs a{};
+  a.x = static_cast<const bf16_t*>(x); a.ldx = ldx;
+  a.w = static_cast<const bf16_t*>(w); a.ldw = ldw;
+  a.out = static_cast<bf16_t*>(h); a.ldo = ldo;
+  a.m = m; a.n = n; a.k = k;
+  a.res = residual; a.ldr = ldr; a.nw = norm_weight; a.hn = static_cast<bf16_t*>(hn); a.ldh = ldh;
+  a.eps = eps; a.cnt = static_cast<unsigned*>(counters);
+  const int rc = pl.form == GemmForm::kTileNorm ? gemm_tile_launch(a, pl, s)
+                                                : linear_dma_launch(a, pl, s);
+  return rc != VM_OK ? rc : vmhost::launch_status("vm_linear_add_norm_fwd");
 }

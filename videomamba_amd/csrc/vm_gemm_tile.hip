@@ -39,7 +39,7 @@
 
 #include <utility>
 
-#include "vm_common.h"
+#include "vm_gemm.h"
 
 namespace vm {
 
@@ -103,7 +103,7 @@ struct TileGemmParams {
   const float* nw;
   bf16_t* hn; long long ldh;
   float eps;
-  unsigned* cnt;  // [0] error word, [16 + row block] producer counts; left zeroed
+  unsigned* cnt;  // [0] error word, [kCntHead + row block] producer counts; left zeroed
 };
 constexpr int kTileSC1 = 16;  // buffer cache-policy bit sc1: agent-coherent (cross-workgroup)
 // rows of the NORM pass each wave has in flight at once (18 VGPRs per row at n = 576)
@@ -132,7 +132,7 @@ __global__ __launch_bounds__(512) void gemm_tile_kernel(const TileGemmParams p) 
   constexpr int WGN = 8 / WGM;
   constexpr int BM = 2 * WGM * TMH * 16, BN = 2 * WGN * TNH * 16;
   constexpr int HA = BM / 2, HB = BN / 2;
-  constexpr int RB = 128;  // bytes per staged row: 64 bf16 of K
+  constexpr int RB = kGemmRow;  // bytes per staged row: 64 bf16 of K
   constexpr int A_BYTES = BM * RB, STAGE = (BM + BN) * RB;
   constexpr int TPI = (NK & 1) ? 2 : 1;  // tiles per loop iteration: stage parity stays static
   constexpr int QI = TPI * NK;           // K-tiles per iteration (even)
@@ -331,7 +331,7 @@ __global__ __launch_bounds__(512) void gemm_tile_kernel(const TileGemmParams p) 
     int ok = 1;
     if (lane == 0) {
       unsigned spins = 0;
-      while (__hip_atomic_load(&p.cnt[16 + mt], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) <
+      while (__hip_atomic_load(&p.cnt[kCntHead + mt], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) <
              static_cast<unsigned>(p.ntn - 1)) {
         if (++spins >= (1u << 20)) {
           __hip_atomic_store(p.cnt, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
@@ -461,7 +461,7 @@ __global__ __launch_bounds__(512) void gemm_tile_kernel(const TileGemmParams p) 
         // every wave's stores of the previous tile completed before this barrier (waves 0-3
         // run one barrier ahead of wave 4): count the producer tile in
         if (sig_mt >= 0 && wave == 4 && lane == 0)
-          __hip_atomic_fetch_add(&p.cnt[16 + sig_mt], 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+          __hip_atomic_fetch_add(&p.cnt[kCntHead + sig_mt], 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
         sig_mt = -1;
       }
       tg_wait_lgkm0();
@@ -487,12 +487,12 @@ __global__ __launch_bounds__(512) void gemm_tile_kernel(const TileGemmParams p) 
             if (wave < 4) tg_barrier();
             tg_barrier();
             if (!poller && wave == 0 && lane == 0)
-              __hip_atomic_fetch_add(&p.cnt[16 + mt], 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+              __hip_atomic_fetch_add(&p.cnt[kCntHead + mt], 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
             norm_pass(pend_mt);
             if (wave >= 4) {
               tg_barrier();  // waves 0-3 have finished their polls and rows
               if (wave == 4 && lane == 0)
-                __hip_atomic_store(&p.cnt[16 + pend_mt], 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+                __hip_atomic_store(&p.cnt[kCntHead + pend_mt], 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
             }
             pend_mt = -1;
           } else if (!poller) {
@@ -523,12 +523,12 @@ __global__ __launch_bounds__(512) void gemm_tile_kernel(const TileGemmParams p) 
   if constexpr (NORM) {
     tg_barrier();  // every wave's stores of the last tile are acknowledged
     if (sig_mt >= 0 && wave == 0 && lane == 0)
-      __hip_atomic_fetch_add(&p.cnt[16 + sig_mt], 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+      __hip_atomic_fetch_add(&p.cnt[kCntHead + sig_mt], 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
     if (pend_mt >= 0) {
       norm_pass(pend_mt);
       tg_barrier();
       if (wave == 0 && lane == 0)
-        __hip_atomic_store(&p.cnt[16 + pend_mt], 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        __hip_atomic_store(&p.cnt[kCntHead + pend_mt], 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
     }
   }
 }
@@ -536,93 +536,46 @@ __global__ __launch_bounds__(512) void gemm_tile_kernel(const TileGemmParams p) 
 // Configurations: (WGM, TMH, TNH) -> BM x BN
 //   wide  (2, 4, 2): 256 x 256, waves 2 (M) x 4 (N), 128 x 64 per wave
 //   narrow (4, 2, 3): 256 x 192, waves 4 x 2, 64 x 96 per wave (out_proj: N = 576 = 3 x 192)
-constexpr int kTileBM = 256;
-constexpr size_t kTileLdsWide = 2 * (256 + 256) * 128;
-constexpr size_t kTileLdsNarrow = 2 * (256 + 192) * 128;
-
-// 0: not supported; 256 or 192: the BN this shape runs with
-int gemm_tile_bn(int m, int n, int k, long long ldx, long long ldw, long long ldo) {
-  if (k % 64 != 0) return 0;
-  switch (k / 64) {
-    case 3: case 6: case 9: case 12: case 18: case 24: break;
-    default: return 0;
-  }
-  const int bn = (n >= 1024 && n % 256 == 0) ? 256 : (n % 192 == 0 ? 192 : (n % 256 == 0 ? 256 : 0));
-  if (!bn) return 0;
-  // per-tile buffer ranges: 256 rows of x / out, bn rows of w
-  if (256LL * ldx * 2 >= (1LL << 31) || 256LL * ldo * 2 >= (1LL << 31) ||
-      static_cast<long long>(bn) * ldw * 2 >= (1LL << 31))
-    return 0;
-  (void)m;
-  return bn;
+// The NORM form (out_proj + the next block's residual add + RMSNorm) runs the narrow one
+// for the (n, k) of VM_GEMM_TILE_NORM_LIST.
+#define VM_TG_K(NKV)                                                                          \
+  case NKV:                                                                                   \
+    hipLaunchKernelGGL((gemm_tile_kernel<WGM, TMH, TNH, NKV>), grid, block, pl.lds, s, p);    \
+    return VM_OK;
+template <int WGM, int TMH, int TNH>
+static int gemm_tile_launch_cfg(const TileGemmParams& p, const GemmPlan& pl, hipStream_t s) {
+  const dim3 grid(pl.gx), block(pl.block);
+  switch (pl.NK) { VM_GEMM_NK_LIST(VM_TG_K) }
+  return gemm_no_instance("gemm_tile_kernel", pl);
 }
-
-long long gemm_tile_count(int m, int n, int bn) {
-  return static_cast<long long>((m + kTileBM - 1) / kTileBM) * (n / bn);
-}
-
-#define VM_TG_K(WGM, TMH, TNH, NKV, LDS)                                                \
-  case NKV:                                                                             \
-    hipLaunchKernelGGL((gemm_tile_kernel<WGM, TMH, TNH, NKV>), grid, dim3(512), LDS, s, p); \
-    break;
-#define VM_TG_CFG(WGM, TMH, TNH, LDS)                                                      \
-  switch (p.k / 64) {                                                                      \
-    VM_TG_K(WGM, TMH, TNH, 3, LDS) VM_TG_K(WGM, TMH, TNH, 6, LDS)                          \
-    VM_TG_K(WGM, TMH, TNH, 9, LDS) VM_TG_K(WGM, TMH, TNH, 12, LDS)                         \
-    VM_TG_K(WGM, TMH, TNH, 18, LDS) VM_TG_K(WGM, TMH, TNH, 24, LDS)                        \
-    default: break;                                                                        \
-  }
-
-// Launch on `workgroups` persistent workgroups (a multiple of 8, one per CU); the shape was
-// accepted by gemm_tile_bn.
-void gemm_tile_launch(const bf16_t* x, long long ldx, const bf16_t* w, long long ldw,
-                      bf16_t* out, long long ldo, int m, int n, int k, int bn, int workgroups,
-                      hipStream_t s) {
-  TileGemmParams p{};
-  p.x = x; p.ldx = ldx; p.w = w; p.ldw = ldw; p.out = out; p.ldo = ldo;
-  p.m = m; p.n = n; p.k = k;
-  p.ntn = n / bn;
-  p.tiles = static_cast<int>(gemm_tile_count(m, n, bn));
-  p.tpx = (p.tiles + 7) / 8;
-  const dim3 grid(workgroups);
-  if (bn == 256) {
-    VM_TG_CFG(2, 4, 2, kTileLdsWide)
-  } else {
-    VM_TG_CFG(4, 2, 3, kTileLdsNarrow)
-  }
-}
-#undef VM_TG_CFG
 #undef VM_TG_K
 
-// The NORM form (out_proj + the next block's residual add + RMSNorm): 256 x 192 tiles,
-// K = 384 / 768 / 1152 with n = 192 / 384 / 576 (VideoMamba Ti / S / M out_proj).
-bool gemm_tile_norm_ok(int n, int k, int bn) {
-  return bn == 192 && ((n == 192 && k == 384) || (n == 384 && k == 768) || (n == 576 && k == 1152));
+#define VM_TG_NORM(NV, KV)                                                                    \
+  case KV / kGemmBK * 8 + (NV + 255) / 256:                                                   \
+    hipLaunchKernelGGL((gemm_tile_kernel<4, 2, 3, KV / kGemmBK, true, (NV + 255) / 256>),     \
+                       grid, block, pl.lds, s, p);                                            \
+    return VM_OK;
+static int gemm_tile_launch_norm(const TileGemmParams& p, const GemmPlan& pl, hipStream_t s) {
+  const dim3 grid(pl.gx), block(pl.block);
+  switch (pl.NK * 8 + pl.NC) { VM_GEMM_TILE_NORM_LIST(VM_TG_NORM) }
+  return gemm_no_instance("gemm_tile_kernel<NORM>", pl);
 }
+#undef VM_TG_NORM
 
-void gemm_tile_norm_launch(const bf16_t* x, long long ldx, const bf16_t* w, long long ldw,
-                           bf16_t* out, long long ldo, float* res, long long ldr, const float* nw,
-                           float eps, bf16_t* hn, long long ldh, unsigned* cnt, int m, int n,
-                           int k, int workgroups, hipStream_t s) {
+// Launch on the plan's persistent workgroups (a multiple of 8, one per CU).
+int gemm_tile_launch(const GemmArgs& a, const GemmPlan& pl, hipStream_t s) {
   TileGemmParams p{};
-  p.x = x; p.ldx = ldx; p.w = w; p.ldw = ldw; p.out = out; p.ldo = ldo;
-  p.m = m; p.n = n; p.k = k;
-  p.ntn = n / 192;
-  p.tiles = static_cast<int>(gemm_tile_count(m, n, 192));
-  p.tpx = ((p.tiles + 7) / 8 + p.ntn - 1) / p.ntn * p.ntn;  // whole row blocks per XCD range
-  p.res = res; p.ldr = ldr; p.nw = nw; p.hn = hn; p.ldh = ldh; p.eps = eps; p.cnt = cnt;
-  const dim3 grid(workgroups);
-  switch (k / 64) {
-    case 6:
-      hipLaunchKernelGGL((gemm_tile_kernel<4, 2, 3, 6, true, 1>), grid, dim3(512), kTileLdsNarrow, s, p);
-      break;
-    case 12:
-      hipLaunchKernelGGL((gemm_tile_kernel<4, 2, 3, 12, true, 2>), grid, dim3(512), kTileLdsNarrow, s, p);
-      break;
-    case 18:
-      hipLaunchKernelGGL((gemm_tile_kernel<4, 2, 3, 18, true, 3>), grid, dim3(512), kTileLdsNarrow, s, p);
-      break;
-    default: break;
+  p.x = a.x; p.ldx = a.ldx; p.w = a.w; p.ldw = a.ldw; p.out = a.out; p.ldo = a.ldo;
+  p.m = a.m; p.n = a.n; p.k = a.k;
+  p.ntn = pl.ntn; p.tiles = pl.tiles; p.tpx = pl.tpx;
+  switch (pl.form) {
+    case GemmForm::kTile256: return gemm_tile_launch_cfg<2, 4, 2>(p, pl, s);
+    case GemmForm::kTile192: return gemm_tile_launch_cfg<4, 2, 3>(p, pl, s);
+    case GemmForm::kTileNorm:
+      p.res = a.res; p.ldr = a.ldr; p.nw = a.nw; p.hn = a.hn; p.ldh = a.ldh; p.eps = a.eps;
+      p.cnt = a.cnt;
+      return gemm_tile_launch_norm(p, pl, s);
+    default: return gemm_no_instance("gemm_tile_kernel", pl);
   }
 }
 

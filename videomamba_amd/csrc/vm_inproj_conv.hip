@@ -510,7 +510,7 @@ extern "C" int vm_in_proj_conv_proj_fwd(
       hipLaunchKernelGGL((inproj_conv_kernel<NKV, NBV>), grid, block, pl.main.lds, s, q);  \
       break;
 #define VM_IC_K(NKV) VM_IC(NKV, 1) VM_IC(NKV, 2) VM_IC(NKV, 3) VM_IC(NKV, 4) VM_IC(NKV, 5)
-    VM_IC_K(3) VM_IC_K(6) VM_IC_K(9) VM_IC_K(12) VM_IC_K(18) VM_IC_K(24)
+    VM_GEMM_NK_LIST(VM_IC_K)
 #undef VM_IC_K
 #undef VM_IC
     default: break;

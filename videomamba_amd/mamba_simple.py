@@ -56,7 +56,9 @@ from . import phase_lock as _phase
 from .gemm_tuning import tuned
 from .layers import round_up, warn_if_grad
 
-_SMALL_GEMM_K = (192, 384, 576, 768, 1152, 1536)  # vm_linear_fwd's unrolled K-step counts
+# vm_linear_fwd's unrolled K-step counts: a mirror of VM_GEMM_NK_LIST (csrc/vm_gemm_plan.h)
+# that tests/test_api_cpu.py checks against the library
+_SMALL_GEMM_K = (192, 384, 576, 768, 1152, 1536)
 
 
 def takes_training_path(module: nn.Module, *tensors: Optional[Tensor], inference_params=None,

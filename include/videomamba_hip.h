@@ -41,6 +41,8 @@
  *                                 names the kernel form (tests, benches)
  *   vm_linear_add_norm_fwd     <- out_proj + the next Block's fused add + RMSNorm
  *                                 (mamba_simple.py:445-446, videomamba.py:141-166)
+ *   vm_linear_wgrad / _dgrad   <- the backward of the same nn.Linear calls under autograd
+ *                                 (mamba_simple.py:333-339, :445-446): weight and input gradient
  *   vm_patch_embed_fwd         <- PatchEmbed Conv3d + pos/temporal embedding add
  *                                 (videomamba.py:359-368, :806-815)
  *
@@ -66,7 +68,7 @@
 extern "C" {
 #endif
 
-#define VM_ABI_VERSION 16
+#define VM_ABI_VERSION 17
 
 #define VM_DTYPE_F32 0
 #define VM_DTYPE_BF16 1
@@ -606,6 +608,38 @@ int vm_linear_add_norm_fwd(const void* x, long long ldx, const void* w, long lon
                            const float* norm_weight, float eps, void* hn, long long ldh,
                            int m, int n, int k, void* counters, long long counter_bytes,
                            vm_stream_t stream);
+
+/*
+ * Projection GEMM backward (ABI v17): the gradients of out = x w^T (vm_linear_fwd without a
+ * bias), x (m, k), w (n, k), dy (m, n), all bf16 with fp32 accumulation.
+ *
+ * vm_linear_wgrad: dw[n, k] = sum over m of dy[m, n] x[m, k].  dy has row stride lddy, x ldx,
+ * dw lddw (elements); dw is stored in dw_dtype (bf16 or fp32), rounded once.  `dtype` is the
+ * operands' and must be VM_DTYPE_BF16.  n % 8 == 0, k % 64 == 0, leading dimensions at least
+ * the width and multiples of 8, 16-byte aligned pointers, m * lddy * 2 and m * ldx * 2 under
+ * 2 GB, `workspace` of at least vm_linear_wgrad_workspace_bytes(m, n, k) bytes: anything else
+ * returns VM_E_INVALID before any launch.  m == 0 writes a zero dw.  Deterministic: no
+ * atomics; a workgroup owns one 128 x 128 tile of dw and one contiguous slice of m and writes
+ * its fp32 partial tile to the workspace, a second kernel adds the slices in slice order.  The
+ * slices depend on (m, n, k) alone, not on the device.
+ * vm_linear_wgrad_workspace_bytes: 4 n k min(max_slices, ceil(m / 256)) with max_slices =
+ * max(4, floor(512 / tiles)), tiles = ceil(n / 128) ceil(k / 128): at most 16 n k + 32 MiB,
+ * and it never shrinks as m grows.  Pure host code.  vm_linear_wgrad_slice_rows: the rows of
+ * m per slice (tests read it).
+ *
+ * vm_linear_dgrad: dx[m, k] = dy[m, n] w[n, k], given wT = w^T (k, n) with row stride ldwT: the
+ * kernels and the plan of vm_linear_fwd with wT as the weight, so a row's bits do not depend
+ * on m.  The reduction length n is one of vm_linear_fwd's k values or 2304; k % 8 == 0;
+ * refusals as vm_linear_fwd.
+ */
+long long vm_linear_wgrad_workspace_bytes(int m, int n, int k);
+long long vm_linear_wgrad_slice_rows(int m, int n, int k);
+int vm_linear_wgrad(const void* dy, long long lddy, const void* x, long long ldx,
+                    void* dw, long long lddw, int dw_dtype, int m, int n, int k, int dtype,
+                    void* workspace, long long workspace_bytes, vm_stream_t stream);
+int vm_linear_dgrad(const void* dy, long long lddy, const void* wT, long long ldwT,
+                    void* dx, long long lddx, int m, int n, int k, int dtype,
+                    vm_stream_t stream);
 
 /*
  * Tubelet patch embed + positional embeddings (Conv3d with kernel = stride = (kt,Ph,Pw);

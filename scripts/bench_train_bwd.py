@@ -10,9 +10,17 @@ vm_add_norm_fwd / _bwd) and once on torch ops under autograd (``"torch"``):
           against the same arithmetic as fp32 torch ops on the GPU
   block   one training ``Block``
   model   the 32-layer ``PretrainVideoMamba``
+``--compare gemm`` (the default since ABI v17) keeps ``train_ops = "hip"`` on both sides and runs
+each leg once with ``options.train_gemm = "hip"`` (in_proj / out_proj through
+``kernels.linear_fn``: vm_linear_fwd, vm_linear_dgrad, vm_linear_wgrad) and once with
+``"library"`` (``F.linear``, library GEMMs under autograd):
+  in_proj   forward + backward of one 576 -> 2304 projection of batch x 1569 rows
+  out_proj  the same for 1152 -> 576
+  block, model  as above
+``--compare ops`` is the comparison described first (conv, norm, block, model).
 Every measurement runs in a child process of its own under a time limit, so a slow leg cannot
 hold the device for minutes.  ``verdict`` says, per leg and batch, whether the HIP median is
-within the torch-op median plus the larger min-to-max spread of the two.
+within the other side's median plus the larger min-to-max spread of the two.
 
     python scripts/bench_train_bwd.py [--batches 8 32] [--reps 20] > profiles/train_bwd_<tag>.json
 """
@@ -26,7 +34,10 @@ import sys
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 DMODEL, DIM, SEQLEN, WIDTH, DEPTH, FRAMES = 576, 1152, 1569, 4, 32, 8
-LEGS = ("conv", "norm", "block", "model")
+LEGS = ("conv", "norm", "in_proj", "out_proj", "block", "model")
+COMPARE = {"ops": (("conv", "norm", "block", "model"), "torch"),
+           "gemm": (("in_proj", "out_proj", "block", "model"), "library")}
+PROJ = {"in_proj": (2 * DIM, DMODEL), "out_proj": (DMODEL, DIM)}  # (n, k)
 
 
 def _time(fn, warmup, reps):
@@ -48,7 +59,7 @@ def _time(fn, warmup, reps):
                 max=round(max(us), 1), mean=round(statistics.fmean(us), 1))
 
 
-def _conv(batch, ops, dev):
+def _conv(batch, ops, gemm, dev):
     import torch
     import torch.nn.functional as F
     from videomamba_amd import kernels as K
@@ -74,7 +85,7 @@ def _conv(batch, ops, dev):
     return hip if ops == "hip" else taps
 
 
-def _norm(batch, ops, dev):
+def _norm(batch, ops, gemm, dev):
     import torch
     from videomamba_amd import kernels as K, options
     g = torch.Generator().manual_seed(batch)
@@ -94,7 +105,26 @@ def _norm(batch, ops, dev):
     return pair
 
 
-def _block(batch, ops, dev):
+def _proj(leg):
+    def make(batch, ops, gemm, dev):
+        import torch
+        from videomamba_amd import kernels as K, options
+        n, k = PROJ[leg]
+        g = torch.Generator().manual_seed(batch)
+        x = torch.randn(batch, SEQLEN, k, generator=g).to(torch.bfloat16).to(dev).requires_grad_(True)
+        w = (torch.randn(n, k, generator=g) * k ** -0.5).to(torch.bfloat16).to(dev).requires_grad_(True)
+        gy = torch.randn(batch, SEQLEN, n, generator=g).to(torch.bfloat16).to(dev)
+
+        def pair():
+            with options.override(train_gemm=gemm):
+                y = K.linear_fn(x, w)
+            torch.autograd.grad(y, [x, w], gy)
+
+        return pair
+    return make
+
+
+def _block(batch, ops, gemm, dev):
     import torch
     from videomamba_amd import options
     from videomamba_amd.videomamba import create_block
@@ -108,14 +138,14 @@ def _block(batch, ops, dev):
     leaves = [h, r] + list(blk.parameters())
 
     def pair():
-        with options.override(train_ops=ops):
+        with options.override(train_ops=ops, train_gemm=gemm):
             ho, ro = blk(h, r)
             torch.autograd.grad([ho, ro], leaves, [gh, gr])
 
     return pair
 
 
-def _model(batch, ops, dev):
+def _model(batch, ops, gemm, dev):
     import torch
     from videomamba_amd import options
     from videomamba_amd.videomamba import PretrainVideoMamba
@@ -127,30 +157,31 @@ def _model(batch, ops, dev):
 
     def pair():
         model.zero_grad(set_to_none=True)
-        with options.override(train_ops=ops):
+        with options.override(train_ops=ops, train_gemm=gemm):
             vis, pool = model(x)
             (pool.float().square().mean() + vis.float().square().mean()).backward()
 
     return pair
 
 
-def child(leg, batch, ops, warmup, reps):
+def child(leg, batch, ops, gemm, warmup, reps):
     import torch
     assert torch.cuda.is_available(), "this benchmark needs the GPU"
     dev = torch.device("cuda", 0)
-    fn = {"conv": _conv, "norm": _norm, "block": _block, "model": _model}[leg](batch, ops, dev)
+    fn = {"conv": _conv, "norm": _norm, "in_proj": _proj("in_proj"), "out_proj": _proj("out_proj"),
+          "block": _block, "model": _model}[leg](batch, ops, gemm, dev)
     t = _time(fn, warmup, reps)
-    return dict(leg=leg, batch=batch, ops=ops, fwd_bwd_us=t,
+    return dict(leg=leg, batch=batch, ops=ops, gemm=gemm, fwd_bwd_us=t,
                 peak_mem_mb=round(torch.cuda.max_memory_allocated() / 2 ** 20))
 
 
-def _run_child(leg, batch, ops, a):
+def _run_child(leg, batch, ops, gemm, a):
     cmd = ["timeout", "-k", "10", str(a.limit), sys.executable, os.path.abspath(__file__),
-           "--child", leg, "--batch", str(batch), "--ops", ops, "--reps", str(a.reps),
-           "--warmup", str(a.warmup)]
+           "--child", leg, "--batch", str(batch), "--ops", ops, "--gemm", gemm,
+           "--reps", str(a.reps), "--warmup", str(a.warmup)]
     run = subprocess.run(cmd, capture_output=True, text=True)
     if run.returncode != 0:
-        return dict(leg=leg, batch=batch, ops=ops, error=f"exit {run.returncode}",
+        return dict(leg=leg, batch=batch, ops=ops, gemm=gemm, error=f"exit {run.returncode}",
                     stderr=run.stderr[-400:])
     return json.loads(run.stdout.strip().splitlines()[-1])
 
@@ -158,38 +189,45 @@ def _run_child(leg, batch, ops, a):
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--batches", type=int, nargs="+", default=[8, 32])
-    ap.add_argument("--legs", nargs="+", choices=LEGS, default=list(LEGS))
+    ap.add_argument("--compare", choices=list(COMPARE), default="gemm")
+    ap.add_argument("--legs", nargs="+", choices=LEGS, default=None)
     ap.add_argument("--reps", type=int, default=20)
     ap.add_argument("--warmup", type=int, default=3)
     ap.add_argument("--limit", type=int, default=240, help="seconds per child")
     ap.add_argument("--child", choices=LEGS)
     ap.add_argument("--batch", type=int, default=8)
     ap.add_argument("--ops", choices=["hip", "torch"], default="hip")
+    ap.add_argument("--gemm", choices=["hip", "library"], default="library")
     a = ap.parse_args()
     if a.reps < 20:
         ap.error("--reps must be at least 20")
     if a.child:
-        print(json.dumps(child(a.child, a.batch, a.ops, a.warmup, a.reps)), flush=True)
+        print(json.dumps(child(a.child, a.batch, a.ops, a.gemm, a.warmup, a.reps)), flush=True)
         return 0
-    out = dict(bench="train_bwd", d_model=DMODEL, d_inner=DIM, seqlen=SEQLEN, depth=DEPTH,
+    legs, other = COMPARE[a.compare]
+    legs = [leg for leg in (a.legs or legs) if leg in legs]
+    out = dict(bench="train_bwd", compare=a.compare, d_model=DMODEL, d_inner=DIM, seqlen=SEQLEN, depth=DEPTH,
                dtype="bf16", reps=a.reps, warmup=a.warmup, timer="device events", results=[],
                verdict=[])
-    for leg in a.legs:
+    for leg in legs:
         for b in a.batches:
             pair = {}
-            for ops in ("hip", "torch"):
-                r = _run_child(leg, b, ops, a)
+            for side in ("hip", other):
+                # the side varies train_ops ("ops") or train_gemm ("gemm"); the ops comparison
+                # keeps the parent's GEMM path, the gemm comparison keeps train_ops = "hip"
+                ops, gemm = (side, "library") if a.compare == "ops" else ("hip", side)
+                r = _run_child(leg, b, ops, gemm, a)
                 out["results"].append(r)
                 if "error" in r:  # a faulted or hung leg: start nothing more on the device
                     print(json.dumps(out), flush=True)
                     return 1
-                pair[ops] = r["fwd_bwd_us"]
+                pair[side] = r["fwd_bwd_us"]
             spread = max(p["max"] - p["min"] for p in pair.values())
-            out["verdict"].append(dict(
-                leg=leg, batch=b, hip_us=pair["hip"]["median"], torch_us=pair["torch"]["median"],
-                spread_us=round(spread, 1),
-                torch_over_hip=round(pair["torch"]["median"] / pair["hip"]["median"], 2),
-                hip_not_slower=pair["hip"]["median"] <= pair["torch"]["median"] + spread))
+            out["verdict"].append({
+                "leg": leg, "batch": b, "hip_us": pair["hip"]["median"],
+                other + "_us": pair[other]["median"], "spread_us": round(spread, 1),
+                other + "_over_hip": round(pair[other]["median"] / pair["hip"]["median"], 2),
+                "hip_not_slower": pair["hip"]["median"] <= pair[other]["median"] + spread})
     print(json.dumps(out), flush=True)
     return 0
 

@@ -20,7 +20,7 @@ LIB_PATH = os.path.join(os.path.dirname(os.path.abspath(__file__)), LIB_NAME)
 
 VM_DTYPE_F32 = 0
 VM_DTYPE_BF16 = 1
-ABI_VERSION = 16
+ABI_VERSION = 17
 
 _P = c_void_p
 _LL = c_longlong
@@ -165,6 +165,14 @@ _SIGNATURES = {
          _P, c_float, _P, _LL,                    # norm weight, eps, hn, ldh
          _I, _I, _I, _P, _LL, _P], _I),           # m, n, k, counters, bytes, stream
     "vm_linear_add_norm_counter_bytes": ([_I], _LL),
+    "vm_linear_wgrad_workspace_bytes": ([_I, _I, _I], _LL),
+    "vm_linear_wgrad_slice_rows": ([_I, _I, _I], _LL),
+    "vm_linear_wgrad": (
+        [_P, _LL, _P, _LL,                        # dy, lddy, x, ldx
+         _P, _LL, _I,                             # dw, lddw, dw dtype
+         _I, _I, _I, _I,                          # m, n, k, dtype
+         _P, _LL, _P], _I),                       # workspace, bytes, stream
+    "vm_linear_dgrad": ([_P, _LL, _P, _LL, _P, _LL, _I, _I, _I, _I, _P], _I),
     "vm_patch_embed_fwd": (
         [_P, _P, _P, _P, _P, _P, _LL, _I, _I, _I, _I, _I, _I, _I, _I, _I, _I, _I,
          _P, _P, _I, _P], _I),

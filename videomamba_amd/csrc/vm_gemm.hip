@@ -416,6 +416,13 @@ static int linear_dma_launch_tile(const LinParams& p, const NormTail& q, const G
                        s, p, q);                                                                \
     return VM_OK;
     VM_GEMM_NK_LIST(VM_LDMA_K)
+    case 36:  // vm_linear_dgrad only (VM_GEMM_DGRAD_NK_LIST): the add + norm form never runs it
+      if constexpr (!NORM) {
+        hipLaunchKernelGGL((linear_dma_kernel<BM, BN, 36, NBUF, NWM, false>), grid, block, pl.lds,
+                           s, p, q);
+        return VM_OK;
+      }
+      break;
 #undef VM_LDMA_K
   }
   return gemm_no_instance("linear_dma_kernel", pl);
@@ -573,4 +580,52 @@ extern "C" int vm_linear_add_norm_fwd(const void* x, long long ldx, const void* 
   const int rc = pl.form == GemmForm::kTileNorm ? gemm_tile_launch(a, pl, s)
                                                 : linear_dma_launch(a, pl, s);
   return rc != VM_OK ? rc : vmhost::launch_status("vm_linear_add_norm_fwd");
+}
+
+// dx[m, k] = dy[m, n] w[n, k]: the forward GEMM with wT = w^T (k, n) as its weight and n as
+// its reduction length, through the same plan and kernels (a row's bits do not depend on m),
+// over VM_GEMM_DGRAD_NK_LIST.
+extern "C" int vm_linear_dgrad(const void* dy, long long lddy, const void* wT, long long ldwT,
+                               void* dx, long long lddx, int m, int n, int k, int dtype,
+                               vm_stream_t stream) {
+  if (!dy || !wT || !dx) {
+    vmhost::set_error("vm_linear_dgrad: null required pointer");
+    return VM_E_INVALID;
+  }
+  hipStream_t s = static_cast<hipStream_t>(stream);
+  GemmPlanIn in{};
+  in.m = m; in.n = k; in.k = n; in.ldx = lddy; in.ldw = ldwT; in.ldo = lddx;
+  in.bf16 = dtype == VM_DTYPE_BF16; in.dgrad = true;
+  in.x_al = vmhost::aligned16(dy); in.w_al = vmhost::aligned16(wT); in.o_al = vmhost::aligned16(dx);
+  GemmPlan pl = plan_linear(in);
+  if (pl.reads_cus) {  // only a call that may launch queries the device
+    in.cus = vmhost::device_cus(s);
+    pl = plan_linear(in);
+  }
+  if (pl.form == GemmForm::kNone) {
+    switch (pl.why) {
+      case GemmWhy::kK:
+        vmhost::set_error("vm_linear_dgrad: n = %d (supported reduction lengths: 192, 384, 576, "
+                          "768, 1152, 1536, 2304)", n);
+        break;
+      case GemmWhy::kXPast2GB:
+        vmhost::set_error("vm_linear_dgrad: dy past 2 GB needs the persistent form (k a multiple "
+                          "of 192 or 256)");
+        break;
+      default:
+        vmhost::set_error("vm_linear_dgrad: bf16 only; n a multiple of 64; k and the leading "
+                          "dimensions multiples of 8 and at least the widths; 16-byte aligned "
+                          "operands, wT under 2 GB");
+    }
+    return VM_E_INVALID;
+  }
+  if (pl.form == GemmForm::kEmpty) return VM_OK;
+  GemmArgs a{};
+  a.x = static_cast<const bf16_t*>(dy); a.ldx = lddy;
+  a.w = static_cast<const bf16_t*>(wT); a.ldw = ldwT;
+  a.out = static_cast<bf16_t*>(dx); a.ldo = lddx;
+  a.m = m; a.n = k; a.k = n;
+  const bool tile = pl.form == GemmForm::kTile256 || pl.form == GemmForm::kTile192;
+  const int rc = tile ? gemm_tile_launch(a, pl, s) : linear_dma_launch(a, pl, s);
+  return rc != VM_OK ? rc : vmhost::launch_status("vm_linear_dgrad");
 }

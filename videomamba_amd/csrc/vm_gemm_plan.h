@@ -26,6 +26,13 @@ constexpr bool gemm_k_ok(int k) {
 #undef VM_GEMM_NK_IS
   return false;
 }
+// vm_linear_dgrad (dx = dy w: the forward kernels with the transposed weight, the reduction
+// running over the forward's n) takes the same list plus 36 steps, VideoMamba-M's in_proj
+// (n = 2304).  The forward entries and the mixer middle keep VM_GEMM_NK_LIST.
+#define VM_GEMM_DGRAD_NK_LIST(X) VM_GEMM_NK_LIST(X) X(36)
+constexpr bool gemm_dgrad_k_ok(int k) {
+  return gemm_k_ok(k) || (k > 0 && k % kGemmBK == 0 && k / kGemmBK == 36);
+}
 
 // LDS-DMA tiles (linear_dma_kernel): bm x bn outputs, nbuf stage buffers of (bm + bn) staged
 // rows, 2 * nwm waves.  Wide outputs (n >= kDmaWideMinN: in_proj) take 128 x 128 with two
@@ -106,6 +113,8 @@ struct GemmPlanIn {
   long long ldr, ldh;
   bool r_al, nw_al, hn_al;  // residual, norm weight, hn
   long long counter_bytes;
+  // vm_linear_dgrad only: K from VM_GEMM_DGRAD_NK_LIST
+  bool dgrad;
 };
 
 struct GemmPlan {
@@ -126,8 +135,9 @@ constexpr long long kGemm2G = 1ll << 31;
 // The persistent tile width of a shape, 0 when it has none: wide n on 256 columns, else 192
 // where it divides n, else 256; each tile's buffer ranges (256 rows of x / out, bn rows of w)
 // under 2^31 bytes.
-inline int gemm_tile_bn(int n, int k, long long ldx, long long ldw, long long ldo) {
-  if (!gemm_k_ok(k)) return 0;
+inline int gemm_tile_bn(int n, int k, long long ldx, long long ldw, long long ldo,
+                        bool dgrad = false) {
+  if (!(dgrad ? gemm_dgrad_k_ok(k) : gemm_k_ok(k))) return 0;
   const int bn = (n >= 1024 && n % kTileBNWide == 0) ? kTileBNWide
                  : n % kTileBNNarrow == 0            ? kTileBNNarrow
                  : n % kTileBNWide == 0              ? kTileBNWide : 0;
@@ -188,7 +198,8 @@ inline void set_dma(GemmPlan& pl, const GemmPlanIn& in, GemmForm form, const Dma
 }
 }  // namespace gemm_detail
 
-// vm_linear_fwd_form.  The order of the tests is the order of the refusals a caller sees.
+// vm_linear_fwd_form and vm_linear_dgrad (in.dgrad).  The order of the tests is the order of
+// the refusals a caller sees.
 inline GemmPlan plan_linear(const GemmPlanIn& in) {
   using namespace gemm_detail;
   GemmPlan pl{};
@@ -199,14 +210,14 @@ inline GemmPlan plan_linear(const GemmPlanIn& in) {
       in.ldx < in.k || in.ldw < in.k || in.ldo < in.n || in.ldx % 8 || in.ldw % 8 ||
       in.ldo % 8 || !in.x_al || !in.w_al || !in.o_al || in.n * in.ldw * 2 >= kGemm2G)
     return refuse(pl, GemmWhy::kShape);
-  if (!gemm_k_ok(in.k)) return refuse(pl, GemmWhy::kK);
+  if (!(in.dgrad ? gemm_dgrad_k_ok(in.k) : gemm_k_ok(in.k))) return refuse(pl, GemmWhy::kK);
   pl.NK = in.k / kGemmBK;
   if (in.m == 0) {
     pl.form = GemmForm::kEmpty;
     return pl;
   }
   pl.reads_cus = true;
-  const int bn = in.has_bias ? 0 : gemm_tile_bn(in.n, in.k, in.ldx, in.ldw, in.ldo);
+  const int bn = in.has_bias ? 0 : gemm_tile_bn(in.n, in.k, in.ldx, in.ldw, in.ldo, in.dgrad);
   if (in.form == 2 && !bn) return refuse(pl, GemmWhy::kTileShape);
   if (in.form == 2 && gemm_tile_wgs(in.cus) < 8) return refuse(pl, GemmWhy::kTileCus);
   if (in.form == 2 || (in.form == 0 && gemm_tile_fills(in.m, in.n, bn, in.cus))) {

@@ -545,7 +545,7 @@ __global__ __launch_bounds__(512) void gemm_tile_kernel(const TileGemmParams p) 
 template <int WGM, int TMH, int TNH>
 static int gemm_tile_launch_cfg(const TileGemmParams& p, const GemmPlan& pl, hipStream_t s) {
   const dim3 grid(pl.gx), block(pl.block);
-  switch (pl.NK) { VM_GEMM_NK_LIST(VM_TG_K) }
+  switch (pl.NK) { VM_GEMM_DGRAD_NK_LIST(VM_TG_K) }  // the plan keeps 36 to the dgrad
   return gemm_no_instance("gemm_tile_kernel", pl);
 }
 #undef VM_TG_K

@@ -12,10 +12,14 @@ Public functions keep the call shapes the reference uses for its third-party ker
 * ``rms_norm_fn`` / ``layer_norm_fn`` <- mamba_ssm Triton layer norm, differentiable
   (``vm_add_norm_bwd``)
 
-plus ``patch_embed`` (PatchEmbed Conv3d + positional adds).  Every function runs the HIP
-kernels of ``libvideomamba_hip.so`` on the tensors' device and current stream; CPU
-tensors raise ``RuntimeError`` (as the reference does at ``mamba_simple.py:304-308``),
-and a missing library raises — there is no fallback path.
+plus ``patch_embed`` (PatchEmbed Conv3d + positional adds), ``linear`` (the projection GEMM)
+and ``linear_fn`` (``F.linear`` for the mixer's in_proj / out_proj, differentiable on the HIP
+GEMMs: ``vm_linear_fwd`` forward, ``vm_linear_dgrad`` / ``vm_linear_wgrad`` backward).  Every
+function runs the HIP kernels of ``libvideomamba_hip.so`` on the tensors' device and current
+stream; CPU tensors raise ``RuntimeError`` (as the reference does at
+``mamba_simple.py:304-308``), and a missing library raises — there is no fallback path
+(``linear_fn`` is ``F.linear`` wherever the HIP GEMMs do not take the call, as the training
+mixer's projections were before it).
 
 The ``*_raw`` launchers take explicit element strides and are what the model uses for
 its padded channel-major layouts.
@@ -597,6 +601,110 @@ def linear(x: Tensor, w: Tensor, b32: Optional[Tensor] = None,
                                         LINEAR_FORMS[form], _stream(x))
     _lib.check(rc, "vm_linear_fwd")
     return out
+
+
+# ------------------------------------------------------------------ projection GEMM backward
+# vm_linear_fwd's reduction lengths (csrc/vm_gemm_plan.h VM_GEMM_NK_LIST) and vm_linear_dgrad's
+# (VM_GEMM_DGRAD_NK_LIST: the same plus 36 steps, VideoMamba-M's in_proj)
+_LINEAR_FWD_K = (192, 384, 576, 768, 1152, 1536)
+_LINEAR_DGRAD_N = _LINEAR_FWD_K + (2304,)
+
+
+def linear_wgrad_workspace_bytes(m: int, n: int, k: int) -> int:
+    return int(_lib.load().vm_linear_wgrad_workspace_bytes(m, n, k))
+
+
+def linear_wgrad_slice_rows(m: int, n: int, k: int) -> int:
+    """Rows of m per slice of ``vm_linear_wgrad``'s reduction (pure host query)."""
+    return int(_lib.load().vm_linear_wgrad_slice_rows(m, n, k))
+
+
+def linear_wgrad_raw(dy, x, dw, m, n, k, stream, workspace: Optional[Tensor] = None):
+    """``vm_linear_wgrad``: dw[n, k] = sum_m dy[m, n] x[m, k].  dy (m, n) and x (m, k) bf16
+    with unit column stride (column-sliced views are fine), dw (n, k) bf16 or fp32,
+    overwritten.  ``workspace`` (a uint8 device buffer) replaces the per-stream scratch."""
+    lib = _lib.load()
+    ws_bytes = linear_wgrad_workspace_bytes(m, n, k)
+    ws = _bwd_workspace(dy.device, stream, ws_bytes, workspace, "linear wgrad")
+    rc = lib.vm_linear_wgrad(_p(dy), dy.stride(0), _p(x), x.stride(0), _p(dw), dw.stride(0),
+                             dtype_code(dw.dtype), m, n, k, dtype_code(x.dtype), _p(ws),
+                             ws_bytes if workspace is None else workspace.numel(), stream)
+    _lib.check(rc, "vm_linear_wgrad")
+
+
+def linear_dgrad(dy: Tensor, wT: Tensor, out: Optional[Tensor] = None) -> Tensor:
+    """``vm_linear_dgrad``: dx (m, k) = dy (m, n) @ wT.T with wT = w.t().contiguous() (k, n),
+    bf16, on the forward's GEMM kernels (a row's bits do not depend on m)."""
+    m, n = dy.shape
+    k = wT.shape[0]
+    if out is None:
+        out = torch.empty((m, k), dtype=dy.dtype, device=dy.device)
+    rc = _lib.load().vm_linear_dgrad(_p(dy), dy.stride(0), _p(wT), wT.stride(0), _p(out),
+                                     out.stride(0), m, n, k, dtype_code(dy.dtype), _stream(dy))
+    _lib.check(rc, "vm_linear_dgrad")
+    return out
+
+
+def _rows16(t: Tensor) -> Tensor:
+    """(rows, cols) with unit column stride and 16-byte aligned rows, copied if it is not."""
+    if t.stride(1) != 1 or t.stride(0) % 8 or t.data_ptr() % 16:
+        t = t.contiguous()
+    return t
+
+
+class _Linear(torch.autograd.Function):
+    """``linear`` forward (the inference GEMM, the same bits), ``linear_dgrad`` and
+    ``linear_wgrad_raw`` backward, on (m, k) x (n, k) bf16 operands without a bias."""
+
+    @staticmethod
+    def forward(ctx, x2, w):
+        ctx.save_for_backward(x2, w)
+        return linear(x2, w)
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, dy):
+        x2, w = ctx.saved_tensors
+        m, k = x2.shape
+        n = w.shape[0]
+        dy = _rows16(dy.to(x2.dtype))
+        dx = dw = None
+        if ctx.needs_input_grad[0]:
+            dx = linear_dgrad(dy, w.t().contiguous())
+        if ctx.needs_input_grad[1]:
+            dw = torch.empty((n, k), dtype=w.dtype, device=w.device)
+            linear_wgrad_raw(dy, x2, dw, m, n, k, _stream(x2))
+        return dx, dw
+
+
+def _linear_fn_hip_ok(x: Tensor, weight: Tensor, bias: Optional[Tensor]) -> bool:
+    """Whether vm_linear_fwd, vm_linear_dgrad and vm_linear_wgrad all take the shape."""
+    if bias is not None or x.dtype != torch.bfloat16 or weight.dtype != torch.bfloat16:
+        return False
+    if not (x.is_cuda and weight.is_cuda and weight.dim() == 2 and x.dim() >= 1):
+        return False
+    n, k = weight.shape
+    m = x.numel() // k if k else 0
+    return (m > 0 and x.shape[-1] == k and k in _LINEAR_FWD_K and n in _LINEAR_DGRAD_N
+            and m * max(n, k) * 2 < (1 << 31))
+
+
+def linear_fn(x: Tensor, weight: Tensor, bias: Optional[Tensor] = None) -> Tensor:
+    """``F.linear(x, weight, bias)`` for x (..., k), differentiable on the HIP GEMMs: with grad
+    mode on, an operand that requires grad, ``options.train_gemm == "hip"`` and a shape the
+    HIP forward, dgrad and wgrad all take (bf16 x and weight, no bias, k one of
+    vm_linear_fwd's, n one of vm_linear_dgrad's reduction lengths) the forward is
+    :func:`linear` — the inference GEMM, the same bits — and the backward
+    ``vm_linear_dgrad`` / ``vm_linear_wgrad``.  x and dy are made row-contiguous with torch
+    ops where they are not; gradients come back in their inputs' dtypes and shapes, and only
+    those that are needed are computed.  Every other case is ``F.linear``."""
+    if (torch.is_grad_enabled() and (x.requires_grad or weight.requires_grad)
+            and options.get().train_gemm == "hip" and _linear_fn_hip_ok(x, weight, bias)):
+        k = weight.shape[1]
+        x2 = _rows16(x.reshape(-1, k))
+        w = _rows16(weight)
+        return _Linear.apply(x2, w).reshape(*x.shape[:-1], weight.shape[0])
+    return torch.nn.functional.linear(x, weight, bias)
 
 
 _CNT = {}

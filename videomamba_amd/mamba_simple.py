@@ -603,9 +603,10 @@ class Mamba(nn.Module):
 
     def _forward_train(self, hs: Tensor, state: Optional[Tuple[Tensor, Tensor]],
                        return_state: bool):
-        """The differentiable mixer (``mamba_simple.py:333-451`` under autograd): the
-        projections as torch ops (library GEMMs), the depthwise conv + SiLU and the scan with
-        their gradients on the HIP kernels (``K.causal_conv1d_fn`` for ``d_conv <= 4``,
+        """The differentiable mixer (``mamba_simple.py:333-451`` under autograd): in_proj and
+        out_proj on the HIP GEMM with its HIP backward under ``options.train_gemm == "hip"``
+        (``K.linear_fn``), else as torch ops like x_proj and dt_proj (library GEMMs), the
+        depthwise conv + SiLU and the scan with their gradients on the HIP kernels (``K.causal_conv1d_fn`` for ``d_conv <= 4``,
         ``K.selective_scan_fn``) over token-major views, rounding points as the inference
         path.  With ``state`` the conv continues from ``conv_state`` and the
         scan from ``ssm_state``; the returned states are new tensors attached to the graph
@@ -619,7 +620,10 @@ class Mamba(nn.Module):
                 self._check_state(conv_state, W, "conv_state", Bsz)
             if ssm_state is not None:
                 self._check_state(ssm_state, N, "ssm_state", Bsz)
-        xz = F.linear(hs, self.in_proj.weight, self.in_proj.bias)  # (B, L, 2D)
+        # in_proj / out_proj: the HIP GEMM and its HIP backward where they take the shape
+        # (K.linear_fn), library GEMMs under autograd otherwise
+        lin = K.linear_fn if options.get().train_gemm == "hip" else F.linear
+        xz = lin(hs, self.in_proj.weight, self.in_proj.bias)  # (B, L, 2D)
         x, z = xz[..., :Dm], xz[..., Dm:]
         if W <= K.CONV_BWD_MAX_WIDTH and options.get().train_ops == "hip":
             # causal depthwise conv + SiLU over [conv_state | x] on the HIP kernel and its HIP
@@ -648,7 +652,7 @@ class Mamba(nn.Module):
             tm(u), tm(dt), A, tm(x_dbl[..., R:R + N]), tm(x_dbl[..., R + N:]), self.D.float(),
             z=tm(z), delta_bias=self.dt_proj.bias.float(), delta_softplus=True,
             initial_state=ssm_state, return_last_state=True)
-        out = F.linear(tm(y), self.out_proj.weight, self.out_proj.bias)
+        out = lin(tm(y), self.out_proj.weight, self.out_proj.bias)
         if not return_state:
             return out
         cs_dtype = conv_state.dtype if conv_state is not None else hs.dtype

@@ -100,6 +100,14 @@ documented options object; tests and sweeps change them with :func:`override`.
                      (vm_causal_conv1d_bwd, vm_add_norm_bwd); "torch": the same arithmetic as
                      torch ops under autograd (the mixer's tap loop, an fp32 add + norm) — the
                      yardstick of scripts/bench_train_bwd.py.  The inference path never reads it.
+    train_gemm       "hip" (default): the differentiable mixer runs in_proj and out_proj through
+                     kernels.linear_fn — the inference GEMM forward (the same bits as .eval()),
+                     vm_linear_dgrad and vm_linear_wgrad backward — wherever the HIP GEMMs take
+                     the shape; "library": both as F.linear (library GEMMs under autograd),
+                     the yardstick of scripts/bench_train_bwd.py (block and model 3 % slower
+                     than "hip" at B = 8 and 32).
+                     x_proj, dt_proj and the patch embed are library GEMMs either way.  The
+                     inference path never reads it.
 
 Options are process-global (not thread-local): the model is driven from one host thread,
 and the sub-batch issue threads of ``batch_stream_lock`` read the caller's options.
@@ -139,6 +147,7 @@ class Options:
     small_gemm_rows: int = 4096
     small_gemm_max_n: int = 1024
     train_ops: str = "hip"
+    train_gemm: str = "hip"
 
     def validate(self) -> None:
         if self.mixer_layout not in _LAYOUTS:
@@ -155,6 +164,8 @@ class Options:
             raise ValueError(f"projection_gemm must be hip / library, got {self.projection_gemm!r}")
         if self.train_ops not in ("hip", "torch"):
             raise ValueError(f"train_ops must be hip / torch, got {self.train_ops!r}")
+        if self.train_gemm not in ("hip", "library"):
+            raise ValueError(f"train_gemm must be hip / library, got {self.train_gemm!r}")
         if self.gemm_tuning not in _TUNING:
             raise ValueError(f"gemm_tuning must be one of {_TUNING}, got {self.gemm_tuning!r}")
 

@@ -68,7 +68,7 @@
 extern "C" {
 #endif
 
-#define VM_ABI_VERSION 17
+#define VM_ABI_VERSION 18
 
 #define VM_DTYPE_F32 0
 #define VM_DTYPE_BF16 1
@@ -193,6 +193,22 @@ int vm_selective_scan_dtproj_fwd(
  * (0 = the single pass), ABI v11: vm_selective_scan_dtproj_fwd's segmented form takes
  * segments of at most 64 steps. */
 int vm_selective_scan_chunk_steps(int batch, int dim, int seqlen, int dstate, int segments);
+
+/* Whether vm_selective_scan_dtproj_fwd takes the mixer's operands of this geometry, and on
+ * which form (ABI v18; pure host code, the entry's own plan and checks on made-up addresses):
+ * token-major bf16 rows padded to a multiple of 8 steps, u / out rows of `dim`, z the right
+ * half of 2 dim-wide xz rows, dt_low | B | C in x_dbl rows of dt_rank + 2 dstate (C directly
+ * after B), W_dt zero-padded to 32 (dt_rank <= 32) or 64 columns, and the workspace and sync
+ * buffer of the size queries.  The segment count is the one the size queries answer for (the
+ * current device, or the cost model's calibration without one); `cus` > 0 stands in for the CU
+ * count the segmented grid must fit (answers 2 and 3), 0 means the current device's (none
+ * without one: never 3).
+ *   0  the entry would refuse (or batch / dim is 0: nothing to run)
+ *   1  the single pass takes it
+ *   2  the segmented form takes it, on a grid of more workgroups than CUs
+ *   3  the segmented form takes it, the whole grid resident at one workgroup per CU */
+int vm_selective_scan_dtproj_fits(int batch, int dim, int seqlen, int dstate, int dt_rank,
+                                  int segments, int cus);
 
 /* Scratch bytes vm_selective_scan_fwd wants for token-major operands of this shape and
  * segment request (0 = the cost model's choice). */
@@ -603,6 +619,31 @@ int vm_linear_fwd_form(const void* x, long long ldx, const void* w, long long ld
  * vm_linear_fwd.
  */
 long long vm_linear_add_norm_counter_bytes(int m);
+
+/*
+ * Fits queries of the projection GEMM (ABI v18): 1 where the entry's plan takes the call, 0
+ * where it refuses.  Pure host code: each builds the plan input its entry builds and asks the
+ * same plan (vm_gemm_plan.h), reads the pointers for their 16-byte alignment only (never
+ * dereferenced; NULL counts as aligned), launches nothing and leaves vm_last_error() alone.
+ * The CU count is the scan size queries' convention: the current device's, or 0 without one
+ * (then no persistent form: x past 2 GB does not fit, and the fused entry has no one-launch
+ * form).  Where every device of a machine has the same CU count this is the entry's answer.
+ *   vm_linear_fits           vm_linear_fwd (form 0) on x (m, k), w (n, k), out (m, n)
+ *   vm_linear_add_norm_fits  vm_linear_add_norm_fwd; counter_bytes as the entry takes it
+ *                            (vm_linear_add_norm_counter_bytes(m) fits)
+ *   vm_linear_fn_fits        vm_linear_fwd, vm_linear_dgrad and vm_linear_wgrad (offered its
+ *                            own query's workspace) all take row-contiguous, 16-byte aligned
+ *                            bf16 operands of x (m, k), w (n, k), m >= 1, with
+ *                            m * max(n, k) * 2 < 2^31 (vm_gemm_plan.h kLinearFnMaxBytes: what
+ *                            kernels.linear_fn is tested up to)
+ */
+int vm_linear_fits(const void* x, const void* w, const void* out, long long ldx, long long ldw,
+                   long long ldo, int has_bias, int m, int n, int k, int dtype);
+int vm_linear_add_norm_fits(const void* x, const void* w, const void* h, const void* residual,
+                            const void* norm_weight, const void* hn, long long ldx,
+                            long long ldw, long long ldo, long long ldr, long long ldh, int m,
+                            int n, int k, long long counter_bytes);
+int vm_linear_fn_fits(int m, int n, int k);
 int vm_linear_add_norm_fwd(const void* x, long long ldx, const void* w, long long ldw,
                            void* h, long long ldo, float* residual, long long ldr,
                            const float* norm_weight, float eps, void* hn, long long ldh,

@@ -54,7 +54,7 @@ for B, L in cases:
     for S in segs:
         if S > (L + 7) // 8:
             continue
-        if DTP and not 0 < K.scan_chunk_steps(B, Dm, L, N, S) <= K.SCAN_DTPROJ_MAX_SEGMENT:
+        if DTP and K.scan_dtproj_fits(B, Dm, L, N, R, S) < 2:  # not the segmented form
             continue
         with options.override(scan_segments=S):
             if DTP:

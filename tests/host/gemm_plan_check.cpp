@@ -1,6 +1,7 @@
 // Stand-alone check of the projection GEMM's host plan (videomamba_amd/csrc/vm_gemm_plan.h):
 // walks plan_linear() and plan_linear_add_norm() over a grid of shapes and exits non-zero
-// unless every plan picks the form the rules below give and is self-consistent.  The rules are
+// unless every plan picks the form the rules below give and is self-consistent, and the fits
+// queries (linear_fits, linear_add_norm_fits, linear_fn_fits) answer as the rules do.  The rules are
 // written out a second time here, as vm_linear_fwd_form and vm_linear_add_norm_fwd had them
 // before the plan (literal numbers, not the header's constants).  Built and run by
 // tests/test_api_cpu.py with -fsanitize=address,undefined; needs no GPU and no HIP.
@@ -9,6 +10,7 @@
 #include <vector>
 
 #include "vm_gemm_plan.h"
+#include "vm_gemm_wgrad_plan.h"
 
 using namespace vm;
 
@@ -33,6 +35,7 @@ constexpr long long k2G = 1ll << 31;
 
 static long g_seen[kGemmForms];
 static long g_plans = 0;
+static long g_fn_fits = 0;
 
 // ---------------------------------------------------------------- the rules, written out
 static bool k_in_list(int k) {
@@ -164,6 +167,21 @@ static void check_linear(const GemmPlanIn& in) {
   CHECK(pl.form == want);
   CHECK(pl.why == why);
   check_common(in, pl);
+  // vm_linear_fits: the plan's own answer, from the input the entries build
+  CHECK(linear_fits(in) == (want != GemmForm::kNone));
+  const GemmPlanIn built = gemm_linear_in(in.m, in.n, in.k, in.ldx, in.ldw, in.ldo, in.has_bias,
+                                          in.bf16, in.form, in.x_al, in.w_al, in.o_al);
+  CHECK(built.cus == 0 && !built.dgrad);
+  GemmPlanIn on = built;
+  on.cus = in.cus;
+  CHECK(linear_fits(on) == (want != GemmForm::kNone) && plan_linear(on).form == want);
+}
+
+// vm_linear_fn_fits as kernels.linear_fn's gate had it before the query: m >= 1, k one of the
+// forward's reduction lengths, n one of dgrad's, m rows of the wider operand under 2^31 bytes
+static bool want_linear_fn(int m, int n, int k) {
+  return m >= 1 && k % 64 == 0 && k_in_list(k) && n % 64 == 0 && (k_in_list(n) || n == 2304) &&
+         2ll * m * (n > k ? n : k) < k2G;
 }
 
 static void check_add_norm(const GemmPlanIn& in) {
@@ -176,6 +194,14 @@ static void check_add_norm(const GemmPlanIn& in) {
   CHECK(pl.counter_bytes == want_counter_bytes(in.m));
   CHECK(pl.counter_bytes == gemm_counter_bytes(in.m));
   check_common(in, pl);
+  // vm_linear_add_norm_fits: the plan's own answer, from the input the entry builds
+  CHECK(linear_add_norm_fits(in) == (want != GemmForm::kNone));
+  GemmPlanIn built = gemm_add_norm_in(in.m, in.n, in.k, in.ldx, in.ldw, in.ldo, in.ldr, in.ldh,
+                                      in.x_al, in.w_al, in.o_al, in.r_al, in.nw_al, in.hn_al,
+                                      in.counter_bytes);
+  CHECK(built.cus == 0 && built.bf16 && !built.has_bias && built.form == 0);
+  built.cus = in.cus;
+  CHECK(plan_linear_add_norm(built).form == want);
   if (pl.form == GemmForm::kTwoLaunch)
     CHECK(in.ldo == in.n && in.ldr == in.n && in.ldh == in.n);
   // the persistent test is vm_linear_fwd's: past the one-launch form, the fused entry runs
@@ -230,6 +256,14 @@ int main() {
             }
           // ---- vm_linear_add_norm_fwd: contiguous operands
           check_add_norm(base(m, n, k, cu));
+          // ---- vm_linear_fn_fits: forward, dgrad and wgrad of one shape
+          {
+            const GemmPlanIn in = base(m, n, k, cu);
+            g_in = &in;
+            CHECK(linear_fn_fits(m, n, k, cu) == want_linear_fn(m, n, k));
+            CHECK(linear_fn_fits(m, k, n, cu) == want_linear_fn(m, k, n));
+            g_fn_fits += linear_fn_fits(m, n, k, cu) + linear_fn_fits(m, k, n, cu);
+          }
           if (k != 0 && k != 96 && k != 576 && k != 1152 && k != 384 && k != 640) continue;
           // ---- leading dimensions: padded, and on both sides of every 2^31-byte limit
           const long long rows_m = m > 0 ? m : 1;
@@ -307,6 +341,10 @@ int main() {
       std::fprintf(stderr, "form %d never planned\n", f);
       ++g_fail;
     }
+  }
+  if (!g_fn_fits) {
+    std::fprintf(stderr, "vm_linear_fn_fits never answered 1\n");
+    ++g_fail;
   }
   std::printf("per form:");
   for (int f = 0; f < kGemmForms; ++f) std::printf(" %ld", g_seen[f]);

@@ -1,6 +1,7 @@
 // Stand-alone check of the selective scan's host plan (videomamba_amd/csrc/vm_scan_plan.h):
 // walks plan_scan() over a grid of shapes, CU counts, operand facts and buffer offers and
-// exits non-zero unless every plan is self-consistent.  Built and run by
+// exits non-zero unless every plan is self-consistent and vm_selective_scan_dtproj_fits'
+// answer (scan_dtproj_route and the two geometry rules) is the one the rules written out give.  Built and run by
 // tests/test_api_cpu.py with -fsanitize=address,undefined; needs no GPU and no HIP.
 #include <cstdio>
 
@@ -31,7 +32,7 @@ int main() {
   const int Cus[] = {64, 256, 304};
   const int Dev[] = {0, 64, 256};
   const int Es[] = {2, 4};
-  long plans = 0, seen[4] = {0, 0, 0, 0}, seen_lbc = 0;
+  long plans = 0, seen[4] = {0, 0, 0, 0}, seen_lbc = 0, fits[4] = {0, 0, 0, 0};
   for (int B : Bs) for (int D : Ds) for (int L : Ls) for (int seg : Ss) for (int cus : Cus) {
     // what the ABI size queries report: no operands, everything on offer
     ScanPlanIn qi{};
@@ -100,6 +101,36 @@ int main() {
       // (f) too little workspace: the single pass
       if (in.ws_offer < q.ws_query) CHECK(pl.form == ScanForm::kSingle);
       if (pl.form == ScanForm::kSingle) CHECK(pl.S == 1 && pl.T == L);
+      // (g) vm_selective_scan_dtproj_fits: the four-way answer against the rules of
+      // seq_dtp_supported / seq_dtp_chunk_supported written out (literal numbers), for every
+      // dt_rank, state count, padded W_dt width and verdict of the operand checks
+      if (!in.dtp) continue;
+      const int Rs[] = {0, 4, 6, 12, 32, 36, 64, 68};
+      const int Ns[] = {8, 16};
+      const int Wds[] = {16, 32, 48, 64};
+      for (int R : Rs) for (int N : Ns) for (int wd : Wds) for (int ops = 0; ops < 2; ++ops) {
+        const bool rank_ok = R >= 1 && R % 4 == 0;
+        const bool single = N == 16 && D % 128 == 0 && rank_ok && R <= 64 &&
+                            wd >= 16 * ((R + 15) / 16) && wd % 4 == 0;
+        const bool chunk = pl.chunked() && N == 16 && (wd == 32 || wd == 64) && rank_ok && R <= wd;
+        CHECK(scan_dtp_single_geom(D, N, R, wd) == single);
+        CHECK(scan_dtp_chunk_geom(pl, N, R, wd) == chunk);
+        int want;
+        if (pl.chosen <= 1) {
+          want = single && ops ? 1 : 0;
+        } else if (!(chunk && ops)) {
+          want = 0;  // a segmented request never falls back to the single pass
+        } else {
+          const long long wgs = static_cast<long long>((D + 63) / 64) * pl.nblk * B;
+          want = wgs <= dev ? 3 : 2;
+          CHECK(pl.T <= 64);
+          // the one-launch form runs exactly where the answer is 3 and the sync buffer is there
+          CHECK((pl.form == ScanForm::kChunk1) == (want == 3 && in.sync_offer >= q.sync_query));
+        }
+        const int got = scan_dtproj_route(pl, single && ops, chunk && ops, B, D, dev);
+        CHECK(got == want);
+        ++fits[got];
+      }
     }
   }
   // the walk reached every form
@@ -109,10 +140,18 @@ int main() {
       ++g_fail;
     }
   }
+  for (int a = 0; a < 4; ++a) {
+    if (!fits[a]) {
+      std::fprintf(stderr, "dtproj fits answer %d never given\n", a);
+      ++g_fail;
+    }
+  }
   if (!seen_lbc) {
     std::fprintf(stderr, "LBC never planned\n");
     ++g_fail;
   }
+  std::printf("dtproj fits: %ld refused, %ld single, %ld segmented, %ld segmented resident\n",
+              fits[0], fits[1], fits[2], fits[3]);
   std::printf("%ld plans: single %ld legacy %ld chunk2 %ld chunk1 %ld lbc %ld, %ld failures\n",
               plans, seen[0], seen[1], seen[2], seen[3], seen_lbc, g_fail);
   return g_fail ? 1 : 0;

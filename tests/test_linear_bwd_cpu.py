@@ -181,23 +181,23 @@ def test_dgrad_entry_refuses_bad_arguments_without_gpu():
     assert lib.vm_linear_dgrad(*_dgrad_args(ptr, m=0, n=2304, k=576)) == 0
 
 
-def test_python_mirrors_of_the_k_lists_match_the_library():
-    """``kernels._LINEAR_FWD_K`` / ``_LINEAR_DGRAD_N`` decide what ``linear_fn`` sends to the
-    HIP GEMMs: the forward's list is the mixer's (itself checked against the library in
-    test_api_cpu.py), the dgrad's is what ``vm_linear_dgrad`` accepts (an m = 0 call is VM_OK
-    exactly for a reduction length of the list; nothing launches)."""
+def test_linear_fn_fits_takes_the_reduction_lengths_the_entries_take():
+    """``kernels.linear_fn_fits`` decides what ``linear_fn`` sends to the HIP GEMMs, from the
+    entries' own plans: its k are the reduction lengths ``vm_linear_fwd`` accepts and its n
+    those ``vm_linear_dgrad`` accepts (an m = 0 call is VM_OK exactly for a reduction length
+    of the list; nothing launches)."""
     from videomamba_amd import kernels as K
-    from videomamba_amd import mamba_simple as ms
     lib = _lib.load()
     host = ctypes.create_string_buffer(256)
     ptr = (ctypes.addressof(host) + 15) // 16 * 16
-    assert K._LINEAR_FWD_K == ms._SMALL_GEMM_K
     taken = tuple(n for n in range(64, 4097, 64)
                   if lib.vm_linear_dgrad(*_dgrad_args(ptr, m=0, n=n, k=192)) == 0)
-    assert taken == K._LINEAR_DGRAD_N
+    assert taken == (192, 384, 576, 768, 1152, 1536, 2304)
     fwd = tuple(k for k in range(64, 4097, 64)
                 if lib.vm_linear_fwd(ptr, k, ptr, k, None, ptr, 192, 0, 192, k, 1, None) == 0)
-    assert fwd == K._LINEAR_FWD_K  # the forward did not widen
+    assert fwd == taken[:-1]  # the forward did not widen
+    assert tuple(n for n in range(64, 4097, 64) if K.linear_fn_fits(129, n, 192)) == taken
+    assert tuple(k for k in range(64, 4097, 64) if K.linear_fn_fits(129, 192, k)) == fwd
 
 
 def test_train_gemm_option_is_validated():

@@ -20,7 +20,7 @@ LIB_PATH = os.path.join(os.path.dirname(os.path.abspath(__file__)), LIB_NAME)
 
 VM_DTYPE_F32 = 0
 VM_DTYPE_BF16 = 1
-ABI_VERSION = 17
+ABI_VERSION = 18
 
 _P = c_void_p
 _LL = c_longlong
@@ -66,6 +66,7 @@ _SIGNATURES = {
          _I, _P, _LL, _P, _LL,    # segments, workspace, sync (ABI v11)
          _P], _I),
     "vm_selective_scan_chunk_steps": ([_I, _I, _I, _I, _I], _I),
+    "vm_selective_scan_dtproj_fits": ([_I, _I, _I, _I, _I, _I, _I], _I),
     "vm_selective_scan_workspace_bytes": ([_I, _I, _I, _I, _I], _LL),
     "vm_selective_scan_sync_bytes": ([_I, _I, _I, _I, _I], _LL),
     "vm_selective_scan_sync_status": ([_P, _LL], _I),
@@ -165,6 +166,12 @@ _SIGNATURES = {
          _P, c_float, _P, _LL,                    # norm weight, eps, hn, ldh
          _I, _I, _I, _P, _LL, _P], _I),           # m, n, k, counters, bytes, stream
     "vm_linear_add_norm_counter_bytes": ([_I], _LL),
+    "vm_linear_fits": ([_P, _P, _P, _LL, _LL, _LL, _I, _I, _I, _I, _I], _I),
+    "vm_linear_add_norm_fits": (
+        [_P, _P, _P, _P, _P, _P,                  # x, w, h, residual, norm weight, hn
+         _LL, _LL, _LL, _LL, _LL,                 # ldx, ldw, ldo, ldr, ldh
+         _I, _I, _I, _LL], _I),                   # m, n, k, counter bytes
+    "vm_linear_fn_fits": ([_I, _I, _I], _I),
     "vm_linear_wgrad_workspace_bytes": ([_I, _I, _I], _LL),
     "vm_linear_wgrad_slice_rows": ([_I, _I, _I], _LL),
     "vm_linear_wgrad": (

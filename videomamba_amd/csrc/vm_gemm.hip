@@ -516,10 +516,9 @@ extern "C" int vm_linear_fwd_form(const void* x, long long ldx, const void* w, l
     return VM_E_INVALID;
   }
   hipStream_t s = static_cast<hipStream_t>(stream);
-  GemmPlanIn in{};
-  in.m = m; in.n = n; in.k = k; in.ldx = ldx; in.ldw = ldw; in.ldo = ldo;
-  in.has_bias = bias != nullptr; in.bf16 = dtype == VM_DTYPE_BF16; in.form = form;
-  in.x_al = vmhost::aligned16(x); in.w_al = vmhost::aligned16(w); in.o_al = vmhost::aligned16(out);
+  GemmPlanIn in = gemm_linear_in(m, n, k, ldx, ldw, ldo, bias != nullptr, dtype == VM_DTYPE_BF16,
+                                 form, vmhost::aligned16(x), vmhost::aligned16(w),
+                                 vmhost::aligned16(out));
   GemmPlan pl = plan_linear(in);
   if (pl.reads_cus) {  // only a call that may launch queries the device
     in.cus = vmhost::device_cus(s);
@@ -537,7 +536,31 @@ extern "C" int vm_linear_fwd_form(const void* x, long long ldx, const void* w, l
   return rc != VM_OK ? rc : vmhost::launch_status("vm_linear_fwd");
 }
 
+// The plan of form 0 on the current device (0 CUs without one): no launch, no error text.
+extern "C" int vm_linear_fits(const void* x, const void* w, const void* out, long long ldx,
+                              long long ldw, long long ldo, int has_bias, int m, int n, int k,
+                              int dtype) {
+  GemmPlanIn in = gemm_linear_in(m, n, k, ldx, ldw, ldo, has_bias != 0, dtype == VM_DTYPE_BF16, 0,
+                                 vmhost::aligned16(x), vmhost::aligned16(w),
+                                 vmhost::aligned16(out));
+  in.cus = vmhost::device_cus(nullptr);
+  return linear_fits(in) ? 1 : 0;
+}
+
 extern "C" long long vm_linear_add_norm_counter_bytes(int m) { return gemm_counter_bytes(m); }
+
+extern "C" int vm_linear_add_norm_fits(const void* x, const void* w, const void* h,
+                                       const void* residual, const void* norm_weight,
+                                       const void* hn, long long ldx, long long ldw,
+                                       long long ldo, long long ldr, long long ldh, int m, int n,
+                                       int k, long long counter_bytes) {
+  GemmPlanIn in = gemm_add_norm_in(m, n, k, ldx, ldw, ldo, ldr, ldh, vmhost::aligned16(x),
+                                   vmhost::aligned16(w), vmhost::aligned16(h),
+                                   vmhost::aligned16(residual), vmhost::aligned16(norm_weight),
+                                   vmhost::aligned16(hn), counter_bytes);
+  in.cus = vmhost::device_cus(nullptr);
+  return linear_add_norm_fits(in) ? 1 : 0;
+}
 
 extern "C" int vm_linear_add_norm_fwd(const void* x, long long ldx, const void* w, long long ldw,
                                       void* h, long long ldo, float* residual, long long ldr,
@@ -549,14 +572,10 @@ extern "C" int vm_linear_add_norm_fwd(const void* x, long long ldx, const void* 
     return VM_E_INVALID;
   }
   hipStream_t s = static_cast<hipStream_t>(stream);
-  GemmPlanIn in{};
-  in.m = m; in.n = n; in.k = k; in.ldx = ldx; in.ldw = ldw; in.ldo = ldo;
-  in.bf16 = true;
-  in.x_al = vmhost::aligned16(x); in.w_al = vmhost::aligned16(w); in.o_al = vmhost::aligned16(h);
-  in.ldr = ldr; in.ldh = ldh;
-  in.r_al = vmhost::aligned16(residual); in.nw_al = vmhost::aligned16(norm_weight);
-  in.hn_al = vmhost::aligned16(hn);
-  in.counter_bytes = counter_bytes;
+  GemmPlanIn in = gemm_add_norm_in(m, n, k, ldx, ldw, ldo, ldr, ldh, vmhost::aligned16(x),
+                                   vmhost::aligned16(w), vmhost::aligned16(h),
+                                   vmhost::aligned16(residual), vmhost::aligned16(norm_weight),
+                                   vmhost::aligned16(hn), counter_bytes);
   GemmPlan pl = plan_linear_add_norm(in);
   if (pl.reads_cus) {  // only a call that may launch queries the device
     in.cus = vmhost::device_cus(s);
@@ -593,10 +612,9 @@ extern "C" int vm_linear_dgrad(const void* dy, long long lddy, const void* wT, l
     return VM_E_INVALID;
   }
   hipStream_t s = static_cast<hipStream_t>(stream);
-  GemmPlanIn in{};
-  in.m = m; in.n = k; in.k = n; in.ldx = lddy; in.ldw = ldwT; in.ldo = lddx;
-  in.bf16 = dtype == VM_DTYPE_BF16; in.dgrad = true;
-  in.x_al = vmhost::aligned16(dy); in.w_al = vmhost::aligned16(wT); in.o_al = vmhost::aligned16(dx);
+  GemmPlanIn in = gemm_linear_in(m, k, n, lddy, ldwT, lddx, false, dtype == VM_DTYPE_BF16, 0,
+                                 vmhost::aligned16(dy), vmhost::aligned16(wT),
+                                 vmhost::aligned16(dx), true);
   GemmPlan pl = plan_linear(in);
   if (pl.reads_cus) {  // only a call that may launch queries the device
     in.cus = vmhost::device_cus(s);

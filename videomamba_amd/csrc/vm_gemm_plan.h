@@ -131,6 +131,35 @@ struct GemmPlan {
 };
 
 constexpr long long kGemm2G = 1ll << 31;
+// What kernels.linear_fn (forward, dgrad and wgrad of one shape) is routed up to: x, dy and dx
+// of m rows each under this many bytes, m * max(n, k) * 2 < kLinearFnMaxBytes.  The plans
+// accept more (the persistent form takes x past 2 GB); nothing past this is tested.
+constexpr long long kLinearFnMaxBytes = kGemm2G;
+
+// The plan input of vm_linear_fwd_form, vm_linear_dgrad (`dgrad`: the caller passes dy / wT /
+// dx with n and k swapped) and vm_linear_fits: the entries and the query build it here, so
+// they cannot disagree.  `cus` 0 until a caller has looked it up.
+inline GemmPlanIn gemm_linear_in(int m, int n, int k, long long ldx, long long ldw,
+                                 long long ldo, bool has_bias, bool bf16, int form, bool x_al,
+                                 bool w_al, bool o_al, bool dgrad = false) {
+  GemmPlanIn in{};
+  in.m = m; in.n = n; in.k = k; in.ldx = ldx; in.ldw = ldw; in.ldo = ldo;
+  in.has_bias = has_bias; in.bf16 = bf16; in.form = form;
+  in.x_al = x_al; in.w_al = w_al; in.o_al = o_al;
+  in.dgrad = dgrad;
+  return in;
+}
+// ... and of vm_linear_add_norm_fwd and vm_linear_add_norm_fits.
+inline GemmPlanIn gemm_add_norm_in(int m, int n, int k, long long ldx, long long ldw,
+                                   long long ldo, long long ldr, long long ldh, bool x_al,
+                                   bool w_al, bool o_al, bool r_al, bool nw_al, bool hn_al,
+                                   long long counter_bytes) {
+  GemmPlanIn in = gemm_linear_in(m, n, k, ldx, ldw, ldo, false, true, 0, x_al, w_al, o_al);
+  in.ldr = ldr; in.ldh = ldh;
+  in.r_al = r_al; in.nw_al = nw_al; in.hn_al = hn_al;
+  in.counter_bytes = counter_bytes;
+  return in;
+}
 
 // The persistent tile width of a shape, 0 when it has none: wide n on 256 columns, else 192
 // where it divides n, else 256; each tile's buffer ranges (256 rows of x / out, bn rows of w)
@@ -270,6 +299,12 @@ inline GemmPlan plan_linear_add_norm(const GemmPlanIn& in) {
   if (in.ldo != in.n || in.ldr != in.n || in.ldh != in.n) return refuse(pl, GemmWhy::kNormStrides);
   pl.form = GemmForm::kTwoLaunch;
   return pl;
+}
+
+// The fits queries: whether the plan takes the call, on `in.cus` CUs.
+inline bool linear_fits(const GemmPlanIn& in) { return plan_linear(in).form != GemmForm::kNone; }
+inline bool linear_add_norm_fits(const GemmPlanIn& in) {
+  return plan_linear_add_norm(in).form != GemmForm::kNone;
 }
 
 }  // namespace vm

@@ -289,6 +289,10 @@ extern "C" long long vm_linear_wgrad_slice_rows(int m, int n, int k) {
   return plan_linear_wgrad_shape(m, n, k).slice_rows;
 }
 
+extern "C" int vm_linear_fn_fits(int m, int n, int k) {
+  return linear_fn_fits(m, n, k, vmhost::device_cus(nullptr)) ? 1 : 0;
+}
+
 extern "C" int vm_linear_wgrad(const void* dy, long long lddy, const void* x, long long ldx,
                                void* dw, long long lddw, int dw_dtype, int m, int n, int k,
                                int dtype, void* workspace, long long workspace_bytes,

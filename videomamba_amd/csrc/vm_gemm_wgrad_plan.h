@@ -28,6 +28,8 @@
 
 #include <cstddef>
 
+#include "vm_gemm_plan.h"
+
 namespace vm {
 
 constexpr int kWgTileN = 128;       // output rows per tile (columns of dy)
@@ -143,6 +145,24 @@ inline WgradPlan plan_linear_wgrad(const WgradPlanIn& in) {
     return refuse(WgradWhy::kPast2GB);
   if (in.workspace_bytes < pl.workspace_bytes) return refuse(WgradWhy::kWorkspace);
   return pl;
+}
+
+// vm_linear_fn_fits: forward, dgrad and wgrad all take row-contiguous, 16-byte aligned bf16
+// operands of x (m, k), w (n, k), on `cus` CUs: plan_linear on x, plan_linear with dgrad on
+// dy (m, n) / wT (k, n), plan_linear_wgrad offered its own query's workspace, under
+// kLinearFnMaxBytes.
+inline bool linear_fn_fits(int m, int n, int k, int cus) {
+  if (m <= 0 || n <= 0 || k <= 0 ||
+      static_cast<long long>(m) * (n > k ? n : k) * 2 >= kLinearFnMaxBytes)
+    return false;
+  GemmPlanIn fwd = gemm_linear_in(m, n, k, k, k, n, false, true, 0, true, true, true);
+  GemmPlanIn dgrad = gemm_linear_in(m, k, n, n, n, k, false, true, 0, true, true, true, true);
+  fwd.cus = dgrad.cus = cus;
+  WgradPlanIn wg{};
+  wg.m = m; wg.n = n; wg.k = k; wg.lddy = n; wg.ldx = k; wg.lddw = k;
+  wg.bf16 = wg.dw_dtype_ok = wg.dy_al = wg.x_al = wg.dw_al = wg.ws_al = true;
+  wg.workspace_bytes = plan_linear_wgrad_shape(m, n, k).workspace_bytes;
+  return linear_fits(fwd) && linear_fits(dgrad) && plan_linear_wgrad(wg).why == WgradWhy::kOk;
 }
 
 }  // namespace vm

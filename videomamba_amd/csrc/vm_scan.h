@@ -87,6 +87,16 @@ bool seq_dtp_supported(const ScanParams& p, const DtpArgs& q, int dtype, int dt_
 void seq_dtp_launch(const ScanParams& p, const DtpArgs& q, int dt_rank, hipStream_t s);
 bool seq_dtp_chunk_supported(const ScanParams& p, const DtpArgs& q, int dtype,
                              const ScanPlan& pl);
+// What vm_selective_scan_dtproj_fwd does with these operands under `pl` (planned with dtp),
+// as scan_dtproj_route (vm_scan_plan.h) numbers it; the entry and the query below both ask
+// here.  `dev_cus` only tells answer 2 from 3.
+int seq_dtp_route(const ScanParams& p, const DtpArgs& q, int dtype, const ScanPlan& pl,
+                  int dev_cus);
+// vm_selective_scan_dtproj_fits: seq_dtp_route of the mixer's token-major bf16 operands of
+// this geometry.  The segment count is the size queries' (the current device's CU count,
+// kCalibCUs without one), so the answer goes with vm_selective_scan_chunk_steps; `cus` > 0
+// stands in for the CU count the grid must fit (0: the current device's, none without one).
+int seq_dtp_fits(int batch, int dim, int seqlen, int dstate, int dt_rank, int segments, int cus);
 void seq_dtp_chunk_launch(const ScanParams& p, const DtpArgs& q, const ScanPlan& pl,
                           void* workspace, void* sync, hipStream_t s);
 

@@ -632,8 +632,9 @@ extern "C" int vm_selective_scan_dtproj_fwd(
                                workspace ? static_cast<size_t>(workspace_bytes) : 0,
                                sync ? static_cast<size_t>(sync_bytes) : 0,
                                static_cast<hipStream_t>(stream));
+  const int route = seq_dtp_route(p, q, dtype, pl, 0);
   if (pl.chosen > 1) {
-    if (!seq_dtp_chunk_supported(p, q, dtype, pl)) {
+    if (!route) {
       vmhost::set_error("%s: the segmented form needs bf16 token-major operands with z, "
                         "softplus, 16 states, C directly after B in the x_dbl rows, segments of "
                         "at most 64 steps (vm_selective_scan_chunk_steps), a (dim, 32 | 64) W_dt "
@@ -644,7 +645,7 @@ extern "C" int vm_selective_scan_dtproj_fwd(
     seq_dtp_chunk_launch(p, q, pl, workspace, sync, static_cast<hipStream_t>(stream));
     return vmhost::launch_status(name);
   }
-  if (!seq_dtp_supported(p, q, dtype, dt_rank)) {
+  if (!route) {
     vmhost::set_error("%s: needs bf16 token-major operands with z, softplus, 16 states, C "
                       "directly after B in the x_dbl rows, dim %% 128 == 0, dt_rank <= 64 and a multiple of 4, "
                       "8-byte aligned dt_low rows and a (dim, >= 16*ceil(r/16)) W_dt", name);
@@ -662,6 +663,11 @@ extern "C" int vm_selective_scan_chunk_steps(int batch, int dim, int seqlen, int
   if (batch <= 0 || dim <= 0 || seqlen < 0 || dstate < 1 || dstate > kMaxN || segments < 0)
     return 0;
   return seq_chunk_steps(batch, dim, seqlen, segments);
+}
+
+extern "C" int vm_selective_scan_dtproj_fits(int batch, int dim, int seqlen, int dstate,
+                                             int dt_rank, int segments, int cus) {
+  return seq_dtp_fits(batch, dim, seqlen, dstate, dt_rank, segments, cus);
 }
 
 extern "C" long long vm_selective_scan_workspace_bytes(int batch, int dim, int seqlen,

@@ -14,6 +14,7 @@
 namespace vm {
 
 constexpr int kMaxN = 16;     // states per channel
+constexpr int kSeqNW = 2;     // single pass: waves (channel groups of 64) per workgroup
 constexpr int kChW = 8;  // segments (waves) per workgroup
 constexpr int kMaxSeg = 256;  // segments per sequence (legacy form)
 constexpr int kChLbcRows = 256;  // steps per block the LDS B|C staging (LBC) holds
@@ -52,6 +53,13 @@ inline int choose_segments(int batch, int dim, int seqlen, int cus) {
     }
   }
   return best;
+}
+
+// Workgroups of the chunked form: one per (64-channel group, block of kChW segments, batch
+// row).  The one-launch form needs them all resident at one workgroup per CU; the mixer folds
+// dt_proj into a segmented scan only where they are (vm_selective_scan_dtproj_fits).
+constexpr long long scan_chunk_grid(int batch, int dim, int nblk) {
+  return static_cast<long long>((dim + 63) / 64) * nblk * batch;
 }
 
 enum class ScanForm {
@@ -134,8 +142,8 @@ inline ScanPlan plan_scan(const ScanPlanIn& in) {
     if (in.dtp && !(in.bc1 && cT <= kChDtpT)) return pl;
     // one launch needs the zeroed sync buffer and every block it waits on resident: the
     // whole grid at one workgroup per CU
-    const long long grid = static_cast<long long>(groups) * cblk * in.batch;
-    const bool one = in.sync_offer >= pl.sync_query && grid <= in.dev_cus;
+    const bool one = in.sync_offer >= pl.sync_query &&
+                     scan_chunk_grid(in.batch, in.dim, cblk) <= in.dev_cus;
     pl.form = one ? ScanForm::kChunk1 : ScanForm::kChunk2;
     pl.S = cS;
     pl.T = pl.seg_len = cT;
@@ -158,6 +166,31 @@ inline ScanPlan plan_scan(const ScanPlanIn& in) {
   pl.hin = states;
   pl.sdel = 2 * states;
   return pl;
+}
+
+// dt_proj inside the scan (vm_selective_scan_dtproj_fwd): the limits of its two forms that
+// the geometry alone decides.  What depends on the operands (strides, alignment, 31-bit
+// extents) is seq_dtp_supported's and seq_dtp_chunk_supported's, which call these.
+// `wdt_ld`: columns of the zero-padded W_dt.
+constexpr bool scan_dtp_single_geom(int dim, int dstate, int dt_rank, int wdt_ld) {
+  return dstate == kMaxN && dim % (64 * kSeqNW) == 0 && dt_rank >= 1 && dt_rank <= 64 &&
+         dt_rank % 4 == 0 && wdt_ld >= 16 * ((dt_rank + 15) / 16) && wdt_ld % 4 == 0;
+}
+// `pl` planned with dtp: chunked only for scalar-load B|C rows with C directly after B,
+// segments of at most kChDtpT steps and enough workspace.
+inline bool scan_dtp_chunk_geom(const ScanPlan& pl, int dstate, int dt_rank, int wdt_ld) {
+  return pl.chunked() && dstate == kMaxN && (wdt_ld == 32 || wdt_ld == 64) && dt_rank >= 1 &&
+         dt_rank <= wdt_ld && dt_rank % 4 == 0;
+}
+// What vm_selective_scan_dtproj_fwd does with a call, and vm_selective_scan_dtproj_fits
+// answers: 0 refused, 1 the single pass, 2 the segmented form on a grid past `dev_cus`, 3 the
+// segmented form with the whole grid resident at one workgroup per CU.  `single_ok` /
+// `chunk_ok`: what the two support checks said of the operands.
+inline int scan_dtproj_route(const ScanPlan& pl, bool single_ok, bool chunk_ok, int batch,
+                             int dim, int dev_cus) {
+  if (pl.chosen <= 1) return single_ok ? 1 : 0;
+  if (!chunk_ok) return 0;
+  return scan_chunk_grid(batch, dim, pl.nblk) <= dev_cus ? 3 : 2;
 }
 
 }  // namespace vm

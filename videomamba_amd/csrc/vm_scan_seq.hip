@@ -45,7 +45,6 @@ typedef float f2 __attribute__((ext_vector_type(2)));
 
 constexpr int kTS = 32;       // steps per LDS block
 constexpr int kPF = 8;        // u / delta / z prefetch distance in steps
-constexpr int kSeqNW = 2;     // waves (channel groups of 64) per workgroup
 constexpr bool kSeqXcdRemap = true;  // grids renumbered per XCD (see scan_seq_kernel)
 constexpr bool kSeqDeltaAhead = true;  // next step's delta computed a step early
 constexpr bool kSeqGateAhead = true;   // next step's output-gate factor computed a step early
@@ -1625,17 +1624,27 @@ static void with_bools(F&& f, bool b, Bs... rest) {
 using vmhost::device_cus;
 static int cus_or_calib(int cus) { return cus > 0 ? cus : kCalibCUs; }
 
-// The stream's device decides the segment count and whether the grid is co-resident.
-ScanPlan seq_plan(const ScanParams& p, int dtype, int segments, bool pair, bool dtp,
-                  size_t workspace_bytes, size_t sync_bytes, hipStream_t s) {
+// The plan of operands on a device of `dev_cus` CUs (0: unknown), which decide the segment
+// count, with `resident_cus` CUs to hold the one-launch grid (the same count, but for
+// vm_selective_scan_dtproj_fits' `cus`).
+static ScanPlan seq_plan_on(const ScanParams& p, int dtype, int segments, bool pair, bool dtp,
+                            size_t workspace_bytes, size_t sync_bytes, int dev_cus,
+                            int resident_cus) {
   ScanPlanIn in{};
   in.batch = p.batch; in.dim = p.dim; in.seqlen = p.seqlen; in.segments = segments;
   in.es = elem_size(dtype);
   in.sgpr_bc = seq_sgpr_bc(p, in.es); in.bc1 = seq_bc1(p, in.es); in.pair = pair; in.dtp = dtp;
-  in.dev_cus = device_cus(s);
-  in.cus = cus_or_calib(in.dev_cus);
+  in.dev_cus = resident_cus;
+  in.cus = cus_or_calib(dev_cus);
   in.ws_offer = workspace_bytes; in.sync_offer = sync_bytes;
   return plan_scan(in);
+}
+
+// A launch entry plans for its stream's device.
+ScanPlan seq_plan(const ScanParams& p, int dtype, int segments, bool pair, bool dtp,
+                  size_t workspace_bytes, size_t sync_bytes, hipStream_t s) {
+  const int cus = device_cus(s);
+  return seq_plan_on(p, dtype, segments, pair, dtp, workspace_bytes, sync_bytes, cus, cus);
 }
 
 // The size queries see no operands and no buffers: the plan of operands that take the
@@ -1787,14 +1796,12 @@ void seq_launch(const ScanParams& p, int dtype, const ScanPlan& pl, void* worksp
 }
 
 bool seq_dtp_supported(const ScanParams& p, const DtpArgs& q, int dtype, int dt_rank) {
-  const int nks = (dt_rank + 15) / 16;
   const long long dl_span = static_cast<long long>(p.out_len) * q.dtl_sl * 2;
   return dtype == VM_DTYPE_BF16 && seq_supported(p, dtype) && seq_sgpr_bc(p, 2) &&
          seq_bc1(p, 2) &&
-         p.dstate == kMaxN && p.z && p.softplus && p.split == p.batch &&
-         p.dim % (64 * kSeqNW) == 0 && dt_rank >= 1 && dt_rank <= 64 && dt_rank % 4 == 0 &&
+         scan_dtp_single_geom(p.dim, p.dstate, dt_rank, q.wdt_ld) &&
+         p.z && p.softplus && p.split == p.batch &&
          q.dt_rank == dt_rank && q.dtl && q.wdt &&
-         q.wdt_ld >= 16 * nks && q.wdt_ld % 4 == 0 &&
          (reinterpret_cast<uintptr_t>(q.wdt) & 7) == 0 &&
          (reinterpret_cast<uintptr_t>(q.dtl) & 7) == 0 && q.dtl_sl % 4 == 0 &&
          q.dtl_sb % 4 == 0 && q.dtl_sl >= dt_rank && dl_span < (1ll << 31) &&
@@ -1806,13 +1813,51 @@ bool seq_dtp_supported(const ScanParams& p, const DtpArgs& q, int dtype, int dt_
 // for scalar-load B|C rows, segments of at most kChDtpT steps and enough workspace.
 bool seq_dtp_chunk_supported(const ScanParams& p, const DtpArgs& q, int dtype,
                              const ScanPlan& pl) {
-  return dtype == VM_DTYPE_BF16 && seq_supported(p, dtype) && pl.chunked() &&
-         p.dstate == kMaxN && p.z && p.softplus && p.split == p.batch &&
-         q.dtl && q.wdt && (q.wdt_ld == 32 || q.wdt_ld == 64) && q.dt_rank >= 1 &&
-         q.dt_rank <= q.wdt_ld && q.dt_rank % 4 == 0 && q.dtl_sl >= q.dt_rank &&
+  return dtype == VM_DTYPE_BF16 && seq_supported(p, dtype) &&
+         scan_dtp_chunk_geom(pl, p.dstate, q.dt_rank, q.wdt_ld) &&
+         p.z && p.softplus && p.split == p.batch && q.dtl && q.wdt && q.dtl_sl >= q.dt_rank &&
          (reinterpret_cast<uintptr_t>(q.dtl) & 7) == 0 && q.dtl_sl % 4 == 0 && q.dtl_sb % 4 == 0 &&
          (reinterpret_cast<uintptr_t>(q.wdt) & 15) == 0 &&
          static_cast<long long>(p.out_len) * q.dtl_sl * 2 < (1ll << 31);
+}
+
+int seq_dtp_route(const ScanParams& p, const DtpArgs& q, int dtype, const ScanPlan& pl,
+                  int dev_cus) {
+  return scan_dtproj_route(pl, seq_dtp_supported(p, q, dtype, q.dt_rank),
+                           seq_dtp_chunk_supported(p, q, dtype, pl), p.batch, p.dim, dev_cus);
+}
+
+// The mixer's operands without their storage: made-up addresses that carry the alignment and
+// the B -> C distance the checks read and are never dereferenced.  Rows padded to a multiple
+// of 8 steps; u / out rows of dim, z the right half of (2 dim)-wide xz rows, dt_low | B | C in
+// x_dbl rows of dt_rank + 2 dstate, W_dt zero-padded to 32 (dt_rank <= 32) or 64 columns.
+int seq_dtp_fits(int batch, int dim, int seqlen, int dstate, int dt_rank, int segments, int cus) {
+  if (batch <= 0 || dim <= 0 || seqlen < 0 || dstate != kMaxN || dt_rank < 0 || segments < 0)
+    return 0;
+  const uintptr_t base = static_cast<uintptr_t>(1) << 40;
+  auto at = [&](int slot, long long elems) {
+    return reinterpret_cast<const bf16_t*>(base * (slot + 1) + 2 * elems);
+  };
+  const long long Lp = (static_cast<long long>(seqlen) + 7) / 8 * 8, E = dt_rank + 2 * dstate;
+  if (Lp > 0x7fffffff) return 0;
+  ScanParams p{};
+  p.batch = batch; p.dim = dim; p.seqlen = seqlen; p.out_len = static_cast<int>(Lp);
+  p.dstate = dstate; p.softplus = 1; p.split = batch;
+  p.u = at(0, 0); p.u_sb = Lp * dim; p.u_sd = 1; p.u_sl = dim;
+  p.out = const_cast<bf16_t*>(at(1, 0)); p.o_sb = Lp * dim; p.o_sd = 1; p.o_sl = dim;
+  p.z = at(2, dim); p.z_sb = Lp * 2 * dim; p.z_sd = 1; p.z_sl = 2 * dim;
+  p.dl_sd = 1;
+  p.B = at(3, dt_rank); p.b_sb = Lp * E; p.b_sn = 1; p.b_sl = E;
+  p.C = at(3, dt_rank + dstate); p.c_sb = Lp * E; p.c_sn = 1; p.c_sl = E;
+  DtpArgs q{};
+  q.dtl = at(3, 0); q.dtl_sb = Lp * E; q.dtl_sl = E;
+  q.wdt = at(4, 0); q.wdt_ld = dt_rank <= 32 ? 32 : 64; q.dt_rank = dt_rank;
+  // the segment count is the size queries' (the current device); `cus` only counts residency
+  const int dev_cus = device_cus(nullptr), resident = cus > 0 ? cus : dev_cus;
+  const size_t all = ~static_cast<size_t>(0);
+  const ScanPlan pl =
+      seq_plan_on(p, VM_DTYPE_BF16, segments, false, true, all, all, dev_cus, resident);
+  return seq_dtp_route(p, q, VM_DTYPE_BF16, pl, resident);
 }
 
 void seq_dtp_chunk_launch(const ScanParams& p, const DtpArgs& q, const ScanPlan& pl,

@@ -352,35 +352,36 @@ def scan_chunk_steps(batch: int, dim: int, seqlen: int, dstate: int, segments: i
     return int(_lib.load().vm_selective_scan_chunk_steps(batch, dim, seqlen, dstate, seg))
 
 
-SCAN_DTPROJ_MAX_SEGMENT = 64  # the segmented dt_proj-in-scan form (ABI v11)
+# steps per segment of the segmented dt_proj-in-scan form (vm_scan_plan.h kChDtpT); the gates
+# ask scan_dtproj_fits, tests and sweeps name it (tests/test_routing_gates_cpu.py pins it)
+SCAN_DTPROJ_MAX_SEGMENT = 64
 CONV_PROJ_SMALL_MAX_BATCH = 8  # the small-batch conv_proj forms (vm_conv_proj_plan.h kSkMaxBatch)
-_SCAN_CHUNK_SEGS_PER_BLOCK = 8  # segments per workgroup of the chunked scan (vm_scan_plan.h kChW)
-_CU_COUNT = {}
 
 
-def _cu_count(device) -> int:
-    idx = torch.device(device).index
-    idx = torch.cuda.current_device() if idx is None else idx
-    if idx not in _CU_COUNT:
-        _CU_COUNT[idx] = int(torch.cuda.get_device_properties(idx).multi_processor_count)
-    return _CU_COUNT[idx]
+def scan_dtproj_fits(batch: int, dim: int, seqlen: int, dstate: int, dt_rank: int,
+                     segments: int = -1, cus: int = 0) -> int:
+    """What ``vm_selective_scan_dtproj_fwd`` does with the mixer's token-major bf16 operands
+    of this geometry (``vm_selective_scan_dtproj_fits``, pure host query): 0 refuses, 1 the
+    single pass, 2 the segmented form on a grid past the CU count, 3 the segmented form with
+    the whole grid at one workgroup per CU.  ``segments`` -1 = ``options.scan_segments``;
+    ``cus`` 0 = the current device's CU count."""
+    seg = int(options.get().scan_segments) if segments < 0 else segments
+    return int(_lib.load().vm_selective_scan_dtproj_fits(batch, dim, seqlen, dstate, dt_rank,
+                                                         seg, cus))
 
 
-def scan_dtproj_segmented_pays(batch: int, dim: int, seqlen: int, dstate: int, device,
-                               segments: int = -1) -> bool:
+def scan_dtproj_segmented_pays(batch: int, dim: int, seqlen: int, dstate: int, device=None,
+                               segments: int = -1, *, cus: int = 0, dt_rank: int = 4) -> bool:
     """Whether the mixer should fold dt_proj into the SEGMENTED scan for this shape: segments
     of at most 64 steps, and a grid that fits the chip at one workgroup per CU.  Each wave's
     dt block lives in LDS (119 KB per workgroup), which admits one workgroup per CU; where
     the plain chunked scan would stack several per CU the folded form measured slower than
     it saves in conv_proj (B = 4 M-16f: 138.6 vs 111.2 us per scan against ~19 us of dt
     rows; B = 1 / 2 with 252-workgroup grids: +1.9 / +1.5 us per scan against 4.7 / ~9 us;
-    profiles/r04v_scan_segments_dtp.jsonl)."""
-    steps = scan_chunk_steps(batch, dim, seqlen, dstate, segments)
-    if not 0 < steps <= SCAN_DTPROJ_MAX_SEGMENT:
-        return False
-    segs = -(-seqlen // steps)
-    nblk = -(-segs // _SCAN_CHUNK_SEGS_PER_BLOCK)
-    return batch * (-(-dim // 64)) * nblk <= _cu_count(device)
+    profiles/r04v_scan_segments_dtp.jsonl).  The library counts the grid
+    (:func:`scan_dtproj_fits`, for the current device whatever ``device`` names; ``dt_rank``
+    defaults to one the kernel takes)."""
+    return scan_dtproj_fits(batch, dim, seqlen, dstate, dt_rank, segments, cus) == 3
 
 
 def scan_dtproj_raw(u, u_s, dtl, dtl_s, dt_rank, wdt_pad, A32, B, b_s, C, c_s, D32, z, z_s,
@@ -603,13 +604,23 @@ def linear(x: Tensor, w: Tensor, b32: Optional[Tensor] = None,
     return out
 
 
+def linear_fits(m: int, n: int, k: int, ldx: int, ldw: int, ldo: int, x_ptr: int = 0,
+                w_ptr: int = 0, out_ptr: int = 0, has_bias: bool = False,
+                dtype: int = _lib.VM_DTYPE_BF16) -> bool:
+    """Whether ``vm_linear_fwd`` takes x (m, k), w (n, k), out (m, n) with these row strides
+    (``vm_linear_fits``: the entry's own plan, pure host query).  The addresses are read for
+    their 16-byte alignment only."""
+    return bool(_lib.load().vm_linear_fits(x_ptr, w_ptr, out_ptr, ldx, ldw, ldo, int(has_bias),
+                                           m, n, k, dtype))
+
+
+def linear_fn_fits(m: int, n: int, k: int) -> bool:
+    """Whether ``vm_linear_fwd``, ``vm_linear_dgrad`` and ``vm_linear_wgrad`` all take
+    row-contiguous bf16 x (m, k), w (n, k) (``vm_linear_fn_fits``, pure host query)."""
+    return bool(_lib.load().vm_linear_fn_fits(m, n, k))
+
+
 # ------------------------------------------------------------------ projection GEMM backward
-# vm_linear_fwd's reduction lengths (csrc/vm_gemm_plan.h VM_GEMM_NK_LIST) and vm_linear_dgrad's
-# (VM_GEMM_DGRAD_NK_LIST: the same plus 36 steps, VideoMamba-M's in_proj)
-_LINEAR_FWD_K = (192, 384, 576, 768, 1152, 1536)
-_LINEAR_DGRAD_N = _LINEAR_FWD_K + (2304,)
-
-
 def linear_wgrad_workspace_bytes(m: int, n: int, k: int) -> int:
     return int(_lib.load().vm_linear_wgrad_workspace_bytes(m, n, k))
 
@@ -685,8 +696,7 @@ def _linear_fn_hip_ok(x: Tensor, weight: Tensor, bias: Optional[Tensor]) -> bool
         return False
     n, k = weight.shape
     m = x.numel() // k if k else 0
-    return (m > 0 and x.shape[-1] == k and k in _LINEAR_FWD_K and n in _LINEAR_DGRAD_N
-            and m * max(n, k) * 2 < (1 << 31))
+    return x.shape[-1] == k and linear_fn_fits(m, n, k)
 
 
 def linear_fn(x: Tensor, weight: Tensor, bias: Optional[Tensor] = None) -> Tensor:
@@ -747,6 +757,16 @@ def counter_buffer(device: torch.device, stream: int, nbytes: int) -> Tensor:
 
 def linear_add_norm_counter_bytes(m: int) -> int:
     return int(_lib.load().vm_linear_add_norm_counter_bytes(m))
+
+
+def linear_add_norm_fits(m: int, n: int, k: int, ldx: int, ldw: int, ldo: int, ldr: int,
+                         ldh: int, ptrs=(0, 0, 0, 0, 0, 0)) -> bool:
+    """Whether ``vm_linear_add_norm_fwd`` takes x (m, k), w (n, k), h / residual / hn (m, n)
+    with these row strides and the counters of :func:`linear_add_norm_counter_bytes`
+    (``vm_linear_add_norm_fits``, pure host query).  ``ptrs``: the addresses of x, w, h,
+    residual, norm weight, hn, read for their 16-byte alignment only."""
+    return bool(_lib.load().vm_linear_add_norm_fits(*ptrs, ldx, ldw, ldo, ldr, ldh, m, n, k,
+                                                    linear_add_norm_counter_bytes(m)))
 
 
 def linear_add_norm_status(buf: Tensor) -> int:

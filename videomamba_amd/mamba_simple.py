@@ -56,10 +56,6 @@ from . import phase_lock as _phase
 from .gemm_tuning import tuned
 from .layers import round_up, warn_if_grad
 
-# vm_linear_fwd's unrolled K-step counts: a mirror of VM_GEMM_NK_LIST (csrc/vm_gemm_plan.h)
-# that tests/test_api_cpu.py checks against the library
-_SMALL_GEMM_K = (192, 384, 576, 768, 1152, 1536)
-
 
 def takes_training_path(module: nn.Module, *tensors: Optional[Tensor], inference_params=None,
                         ssm_state=None) -> bool:
@@ -77,9 +73,12 @@ def _small_gemm_ok(x: Tensor, w: Tensor, b: Optional[Tensor], out: Optional[Tens
                    clips: Optional[int] = None) -> bool:
     """Whether a bf16 projection runs on the HIP GEMM (vm_linear_fwd) instead of the library.
 
-    ``options.projection_gemm == "hip"`` (default): whenever the HIP GEMM takes the shape
-    (bf16, no bias, K in its unrolled set, 16-byte rows; x past 2 GB only on the persistent
-    form, n a multiple of 192 or 256).  Its two kernel forms compute every output element as
+    ``options.projection_gemm == "hip"`` (default): whenever the HIP GEMM takes the call.
+    What it takes (K in its unrolled set, 16-byte rows, operand extents; x past 2 GB only
+    where the persistent form fills the chip) is ``vm_linear_fwd``'s own plan, asked through
+    ``K.linear_fits``; the rules here are the mixer's policy: bf16 on the device, and no
+    bias (the library takes one, the mixer's routing does not send one).  Its two kernel
+    forms compute every output element as
     the same MFMA chain in K order, so a row's bits never depend on the row count: a chunked
     stream equals the one-pass forward at every batch (C4 at 72 clips was 1.4e-4 on the
     library GEMM, whose kernel choice depends on M), and at the bench batch the persistent
@@ -87,21 +86,22 @@ def _small_gemm_ok(x: Tensor, w: Tensor, b: Optional[Tensor], out: Optional[Tens
     ``"library"``: the round-3 rule — the HIP GEMM for mixers of at most
     ``row_invariant_gemm_clips`` clips (C5, 16 x 64-frame chunks vs one 1,024-frame pass:
     6.2e-4 relative on the library, 0.0 here; scripts/diag/c5_invariance.py) and for one
-    clip's narrow projections; hipBLASLt otherwise."""
+    clip's narrow projections, x under 2 GB; hipBLASLt otherwise."""
     o = options.get()
-    ok16 = lambda t: t.data_ptr() % 16 == 0 and t.stride(0) % 8 == 0 and t.stride(1) == 1  # noqa: E731
-    if not (x.shape[0] > 0 and b is None and x.dtype == torch.bfloat16
-            and w.dtype == torch.bfloat16 and x.is_cuda and x.shape[1] in _SMALL_GEMM_K
-            and w.shape[0] % 8 == 0 and ok16(x) and ok16(w) and (out is None or ok16(out))):
+    m, k = x.shape
+    n = w.shape[0]
+    if not (m > 0 and b is None and x.dtype == torch.bfloat16 and w.dtype == torch.bfloat16
+            and x.is_cuda and x.stride(1) == 1 and w.stride(1) == 1
+            and (out is None or out.stride(1) == 1)):
         return False
-    small_x = x.shape[0] * x.stride(0) * 2 < (1 << 31)
-    if o.projection_gemm == "hip":
-        return small_x or w.shape[0] % 192 == 0 or w.shape[0] % 256 == 0
-    if not small_x:
+    if o.projection_gemm == "library" and not (
+            m * x.stride(0) * 2 < (1 << 31)
+            and ((clips is not None and 0 < clips <= o.row_invariant_gemm_clips)
+                 or (m <= o.small_gemm_rows and n <= o.small_gemm_max_n))):
         return False
-    if clips is not None and 0 < clips <= o.row_invariant_gemm_clips:
-        return True
-    return x.shape[0] <= o.small_gemm_rows and w.shape[0] <= o.small_gemm_max_n
+    # out None: _linear's fresh (m, n) buffer, aligned by the allocator
+    return K.linear_fits(m, n, k, x.stride(0), w.stride(0), n if out is None else out.stride(0),
+                         x.data_ptr(), w.data_ptr(), 0 if out is None else out.data_ptr())
 
 
 def _linear(x: Tensor, w: Tensor, b: Optional[Tensor] = None,
@@ -286,7 +286,10 @@ class Mamba(nn.Module):
                             tm: bool = True) -> bool:
         """The fused conv + x_proj (+ dt_proj) kernel applies: bf16, its shape limits and,
         token-major (``tm``), buffer extents its 31-bit offsets cover (vm_conv_proj_fits: a
-        very long sequence at batch > 8 takes the unfused conv + projection path)."""
+        very long sequence at batch > 8 takes the unfused conv + projection path).  The shape
+        limits stay here for both layouts: d_inner % 64, d_conv <= 4, R + 2N <= 128, R <= 64
+        and seqlen >= 1 are the argument checks of vm_conv_proj_fwd / vm_conv_proj_cm_fwd
+        themselves, not plan_conv_proj's, so vm_conv_proj_fits does not answer them."""
         E = self.dt_rank + 2 * self.d_state
         if not (hn.dtype == torch.bfloat16 and seqlen >= 1 and self.d_inner % 64 == 0
                 and self.d_conv <= 4 and E <= 128 and self.dt_rank <= 64
@@ -358,7 +361,8 @@ class Mamba(nn.Module):
 
     def _dtp_ok(self, hn: Tensor, seqlen: int, conv_state_in: Optional[Tensor] = None) -> bool:
         """Fold dt_proj into the scan (vm_selective_scan_dtproj_fwd, conv_proj then writes no
-        dt rows): bf16 fused conv_proj path, 16 states, dt_rank a multiple of 4, and
+        dt rows): the bf16 fused conv_proj path, a shape the entry takes (K.scan_dtproj_fits:
+        16 states, dt_rank a multiple of 4, ...), and
           * a segmented scan (streaming batches) of at most 64 steps per segment whose grid
             fits the chip at one workgroup per CU (K.scan_dtproj_segmented_pays; "on": any
             grid): each segment
@@ -371,20 +375,13 @@ class Mamba(nn.Module):
             invariance."""
         mode = options.get().scan_dt_proj
         Bsz = hn.shape[0]
-        if mode == "off":
+        if mode == "off" or not self._fused_conv_proj_ok(hn, seqlen, conv_state_in):
             return False
-        if not (self._fused_conv_proj_ok(hn, seqlen, conv_state_in) and self.d_state == 16
-                and self.dt_rank <= 64 and self.dt_rank % 4 == 0):
-            return False
-        steps = K.scan_chunk_steps(Bsz, self.d_inner, seqlen, self.d_state)
-        if steps > 0:
-            if mode == "on":
-                return steps <= K.SCAN_DTPROJ_MAX_SEGMENT
-            return K.scan_dtproj_segmented_pays(Bsz, self.d_inner, seqlen, self.d_state,
-                                                hn.device)
-        if mode == "auto" and Bsz <= K.CONV_PROJ_SMALL_MAX_BATCH:
-            return False
-        return self.d_inner % 128 == 0
+        # 0 refused, 1 single pass, 2 segmented on a grid past the CUs, 3 segmented and resident
+        fits = K.scan_dtproj_fits(Bsz, self.d_inner, seqlen, self.d_state, self.dt_rank)
+        if mode == "on":
+            return fits != 0
+        return fits == 3 or (fits == 1 and Bsz > K.CONV_PROJ_SMALL_MAX_BATCH)
 
     def _tm_front(self, hn, seqlen, conv_state_in, conv_state_out, bufs=None, want_dt=True):
         """in_proj -> conv + silu -> x_proj -> dt_proj of the token-major form: (xz, u,
@@ -535,11 +532,17 @@ class Mamba(nn.Module):
             log.append((ev0, _scan_event(log), Bsz))
         if (next_norm is not None and next_norm.residual is not None
                 and _small_gemm_ok(y, self.out_proj.weight, self.out_proj.bias, clips=Bsz)):
-            # out_proj + the next block's residual add + RMSNorm in one kernel
-            out = K.linear_add_norm(y, self.out_proj.weight, next_norm.residual.view(-1, C),
-                                    next_norm.w32, next_norm.eps, next_norm.hn.view(-1, C))
-            next_norm.done = True
-            return out.view(Bsz, Lp, C)
+            # out_proj + the next block's residual add + RMSNorm in one kernel, where that
+            # entry's own plan takes the buffers (the routing policy is _small_gemm_ok's)
+            w = self.out_proj.weight
+            res, hn2 = next_norm.residual.view(-1, C), next_norm.hn.view(-1, C)
+            if K.linear_add_norm_fits(
+                    y.shape[0], C, Dm, y.stride(0), w.stride(0), C, res.stride(0), hn2.stride(0),
+                    (y.data_ptr(), w.data_ptr(), 0, res.data_ptr(), next_norm.w32.data_ptr(),
+                     hn2.data_ptr())):
+                out = K.linear_add_norm(y, w, res, next_norm.w32, next_norm.eps, hn2)
+                next_norm.done = True
+                return out.view(Bsz, Lp, C)
         out = _linear(y, self.out_proj.weight, self.out_proj.bias, clips=Bsz)  # (n, C)
         return out.view(Bsz, Lp, C)
 

@@ -768,10 +768,10 @@ class PretrainVideoMamba(nn.Module):
         """Every mixer projection of a bf16 forward of ``part``-clip sub-batches of ``x``
         runs on the HIP GEMM (whose rows do not depend on the row count):
         ``options.projection_gemm == "hip"``, one bf16 dtype over the model, the token-major
-        mixer, in_proj / out_proj K in vm_linear_fwd's unrolled set, no projection bias, and
-        the fused conv_proj for x_proj (dt_proj runs in it or in the scan) at the sub-batch's
-        extents (the longest chunk kind: with the CLS row)."""
-        from .mamba_simple import _SMALL_GEMM_K
+        mixer, in_proj / out_proj shapes vm_linear_fwd takes at the sub-batch's row count
+        (``K.linear_fits``), no projection bias, and the fused conv_proj for x_proj (dt_proj
+        runs in it or in the scan) at the sub-batch's extents (the longest chunk kind: with the
+        CLS row)."""
         o = options.get()
         if (o.projection_gemm != "hip" or o.mixer_layout == "cm"
                 or self._features_dtype() != torch.bfloat16):
@@ -780,11 +780,17 @@ class PretrainVideoMamba(nn.Module):
         L = self._validate_temporal_length(x.shape[2]) * gh * gw + 1
         hn = torch.empty((1, 1, self.embed_dim), dtype=torch.bfloat16,
                          device=x.device).expand(part, round_up(L), self.embed_dim)
+        rows = part * round_up(L)
+
+        def fits(w: Tensor) -> bool:  # contiguous (rows, k) x w (n, k) -> (rows, n)
+            n, k = w.shape
+            return w.stride(1) == 1 and K.linear_fits(rows, n, k, k, w.stride(0), n,
+                                                      w_ptr=w.data_ptr())
+
         for layer in self.layers:
             mx = layer.mixer
-            if (mx.in_proj.weight.shape[1] not in _SMALL_GEMM_K
-                    or mx.out_proj.weight.shape[1] not in _SMALL_GEMM_K
-                    or mx.in_proj.bias is not None or mx.out_proj.bias is not None
+            if (mx.in_proj.bias is not None or mx.out_proj.bias is not None
+                    or not fits(mx.in_proj.weight) or not fits(mx.out_proj.weight)
                     or not mx._fused_conv_proj_ok(hn, L)):
                 return False
         return True

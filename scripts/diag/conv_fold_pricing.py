@@ -42,8 +42,9 @@ xz = torch.empty(m, 2 * mx.d_inner, device=dev, dtype=torch.bfloat16)
 with torch.no_grad():
     out["in_proj_us"] = round(_event_us(
         lambda: K.linear(hn.view(m, C), mx.in_proj.weight, out=xz, form="persistent"), 10), 1)
+    _, _, _, cw, cb = mx._fp32_params()
     out["front_us"] = round(_event_us(
-        lambda: mx._tm_front(hn, 3137, None, None, want_dt=False), 10), 1)
+        lambda: mx._tm_front(hn, 3137, None, None, cw, cb, want_dt=False), 10), 1)
     out["conv_proj_us"] = round(out["front_us"] - out["in_proj_us"], 1)
     del xz
     u = torch.randn(m, mx.d_inner, device=dev, generator=g).to(torch.bfloat16)

@@ -263,6 +263,31 @@ def test_library_loads_and_exports_every_header_symbol():
     raw = ctypes.CDLL(_lib.LIB_PATH)
     for name in declared:
         assert getattr(raw, name) is not None
+    # the types too: every prototype against the hand-written ctypes table, argument by
+    # argument.  A declarator this parser does not know fails (KeyError), it is not skipped.
+    code = re.sub(r"/\*.*?\*/", " ", header, flags=re.S)
+    code = re.sub(r"//[^\n]*", " ", code)
+    code = "\n".join(ln for ln in code.splitlines() if not ln.lstrip().startswith("#"))
+    scalars = {"int": ctypes.c_int, "long long": ctypes.c_longlong, "float": ctypes.c_float,
+               "vm_stream_t": ctypes.c_void_p}
+    returns = {**scalars, "const char*": ctypes.c_char_p}
+
+    def ctype(decl):  # "const float* A" -> c_void_p, "long long u_sb" -> c_longlong
+        m = re.fullmatch(r"(?:const\s+)?(\w+(?:\s+\w+)*?)\s*(\*?)\s*(\w+)", " ".join(decl.split()))
+        assert m, f"unparsed declarator {decl!r}"
+        return ctypes.c_void_p if m.group(2) else scalars[m.group(1)]
+
+    protos = re.findall(r"([\w ]+?\*?)\s*\b(vm_\w+)\s*\(([^)]*)\)\s*;", code)
+    parsed = {}
+    for ret, name, params in protos:
+        params = params.strip()
+        args = [] if params in ("", "void") else [ctype(p) for p in params.split(",")]
+        parsed[name] = (args, returns[" ".join(ret.split())])
+    assert len(parsed) == len(protos) == 43 and set(parsed) == declared
+    assert "vm_" not in re.sub(r"\bvm_\w+\s*\([^)]*\)\s*;|\bvm_stream_t\b", "", code), \
+        "a vm_ declaration the prototype pattern did not take"
+    for name, want in parsed.items():
+        assert (list(_lib._SIGNATURES[name][0]), _lib._SIGNATURES[name][1]) == want, name
 
 
 def test_abi_rejects_bad_arguments_without_gpu():
@@ -784,9 +809,113 @@ def test_sync_rearm_clears_only_the_error_word():
     words = buf.view(torch.int32)
     words[0], words[1], words[2] = 1, 41, 3
     with pytest.raises(RuntimeError):
-        K._SYNC[("cpu", None, 0)] = buf
+        K._SYNC.cache[("cpu", None, 0)] = buf
         try:
             K.check_scan_sync()
         finally:
-            del K._SYNC[("cpu", None, 0)]
+            del K._SYNC.cache[("cpu", None, 0)]
     assert words[0] == 0 and words[1] == 41 and words[2] == 3
+
+
+# ------------------------------------------------------------------ the launch layer
+def _buffer_kinds():
+    from videomamba_amd import kernels as K
+    # (cache, override, get, buffers check_* walks | None, fill is zeros, least size,
+    #  no bytes gives None, an undersized override raises)
+    return {
+        "scratch": (K._SCRATCH, K.scratch_override, K.scratch, None, False, 0, True, True),
+        "sync": (K._SYNC, K.sync_override, K.sync_buffer, K._SYNC.used, True, 4096, True, False),
+        "counters": (K._COUNTERS, K.counter_override, K.counter_buffer, K._COUNTERS.used, True,
+                     4096, False, True),
+    }
+
+
+@pytest.mark.parametrize("kind", ["scratch", "sync", "counters"])
+def test_buffer_kinds_keep_their_rules(kind):
+    """The three per-stream buffer kinds of kernels.py, cell by cell: fill, allocation size,
+    what no bytes gives, what an undersized override does, whether overrides are remembered
+    for check_*; and what they share: the key, growth by replacement, one buffer per stream."""
+    import gc
+    cache, override, get, used, zeroed, floor, empty_none, small_raises = _buffer_kinds()[kind]
+    cpu = torch.device("cpu")
+    s1, s2 = 0xB0F1, 0xB0F2  # made-up streams no other test uses
+    try:
+        a = get(cpu, s1, 8)
+        assert a.dtype == torch.uint8 and a.numel() == max(8, floor)
+        assert cache.cache[("cpu", None, s1)] is a and get(cpu, s1, 8) is a
+        if zeroed:
+            assert not a.any()
+        b = get(cpu, s2, 8)  # a second stream, a second buffer
+        assert b is not a and cache.cache[("cpu", None, s2)] is b
+        big = get(cpu, s1, a.numel() + 64)  # growth replaces the cached buffer
+        assert big is not a and big.numel() == a.numel() + 64
+        assert cache.cache[("cpu", None, s1)] is big and get(cpu, s1, 8) is big
+        if zeroed:
+            assert not big.any()
+        if empty_none:
+            assert get(cpu, s1, 0) is None and get(cpu, s1, -1) is None
+        else:
+            assert get(cpu, s1, 0) is big
+            del cache.cache[("cpu", None, s1)]
+            assert get(cpu, s1, 0).numel() == floor
+        ov = torch.zeros(32, dtype=torch.uint8)
+        with override(ov) as entered:
+            assert entered is ov and get(cpu, s1, 32) is ov and get(cpu, s2, 8) is ov
+            if small_raises:
+                with pytest.raises(RuntimeError, match="_override buffer too small: 32 < 64"):
+                    get(cpu, s1, 64)
+            else:
+                assert get(cpu, s1, 64) is None
+            inner = torch.zeros(16, dtype=torch.uint8)
+            with override(inner):
+                assert get(cpu, s1, 8) is inner
+            assert get(cpu, s1, 8) is ov
+        assert get(cpu, s2, 8) is b
+        if used is None:
+            return
+        ids = lambda: [id(t) for t in used()]  # noqa: E731
+        assert id(ov) in ids() and id(inner) in ids() and id(b) in ids()
+        gone = id(ov)
+        del ov, entered
+        gc.collect()
+        assert gone not in ids() and id(inner) in ids()
+    finally:
+        cache.cache.pop(("cpu", None, s1), None)
+        cache.cache.pop(("cpu", None, s2), None)
+
+
+@pytest.fixture(scope="module")
+def launch_gen():
+    import importlib.util
+    spec = importlib.util.spec_from_file_location(
+        "gen_launch_args", os.path.join(ROOT, "tests", "golden", "gen_launch_args.py"))
+    mod = importlib.util.module_from_spec(spec)
+    spec.loader.exec_module(mod)
+    return mod
+
+
+def test_launchers_pass_the_recorded_arguments(launch_gen):
+    """Every launcher of kernels.py against tests/golden/launch_args.json, recorded by
+    tests/golden/gen_launch_args.py at the commit the table names: the same entry and the same
+    argument list, launch by launch, and no entry Python launches left out."""
+    table = json.load(open(os.path.join(ROOT, "tests", "golden", "launch_args.json")))
+    assert table["commit"] and set(table["cases"]) == {c.__name__ for c in launch_gen.CASES}
+    seen, launches = set(), 0
+    for case in launch_gen.CASES:
+        got = json.loads(json.dumps(launch_gen.run_case(case)))
+        want = table["cases"][case.__name__]
+        assert [c[0] for c in got] == [c[0] for c in want], case.__name__
+        for (entry, a), (_, b) in zip(got, want):
+            assert a == b, (case.__name__, entry, [i for i, (p, q) in enumerate(zip(a, b))
+                                                   if p != q])
+        seen.update(c[0] for c in got)
+        launches += len(got)
+    assert launches == table["launches"]
+    assert seen == launch_gen.launched_entries()
+    # with and without the optional tensors: every entry was recorded with some operand once
+    # absent (null, or a buffer the launcher allocated itself) and once given by the caller
+    kind = lambda p: "null" if p is None else "own" if p == "nonnull" else "given"  # noqa: E731
+    for entry in seen:
+        rows = [c[1] for calls in table["cases"].values() for c in calls if c[0] == entry]
+        ptrs = [i for i, t in enumerate(_lib._SIGNATURES[entry][0][:-1]) if t is ctypes.c_void_p]
+        assert any({"given"} < {kind(r[i]) for r in rows} for i in ptrs), entry

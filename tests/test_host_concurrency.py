@@ -22,22 +22,22 @@ def test_override_slots_are_per_thread():
 
     def other():
         entered.wait(5)
-        seen["ws"] = K._WS_OVERRIDE.value
-        seen["sync"] = K._SYNC_OVERRIDE.value
-        seen["cnt"] = K._CNT_OVERRIDE.value
+        seen["ws"] = K._SCRATCH.slot.value
+        seen["sync"] = K._SYNC.slot.value
+        seen["cnt"] = K._COUNTERS.slot.value
         seen["scratch"] = K.scratch(torch.device("cpu"), 7, 8)
         done.set()
 
     t = threading.Thread(target=other)
     t.start()
     with K.scratch_override(bufs[0]), K.sync_override(bufs[1]), K.counter_override(bufs[2]):
-        assert K._WS_OVERRIDE.value is bufs[0] and K.scratch(torch.device("cpu"), 0, 8) is bufs[0]
+        assert K._SCRATCH.slot.value is bufs[0] and K.scratch(torch.device("cpu"), 0, 8) is bufs[0]
         entered.set()
         done.wait(5)
     t.join(5)
     assert seen["ws"] is None and seen["sync"] is None and seen["cnt"] is None
     assert seen["scratch"] is not bufs[0] and seen["scratch"].numel() >= 8
-    assert K._WS_OVERRIDE.value is None and K._CNT_OVERRIDE.value is None
+    assert K._SCRATCH.slot.value is None and K._COUNTERS.slot.value is None
 
 
 class _FakeTunable:

@@ -74,19 +74,43 @@ def f32c(t: Optional[Tensor]) -> Optional[Tensor]:
     return t.contiguous()
 
 
-def f32_cached(owner, t: Optional[Tensor], slot: str) -> Optional[Tensor]:
-    """fp32 contiguous copy of a small parameter cached on ``owner`` (a module) and
-    refreshed when the parameter changes (data pointer, version, dtype or device)."""
-    if t is None:
-        return None
-    key = (t.data_ptr(), t._version, t.dtype, t.device)
-    cache = owner.__dict__.setdefault("_vm_f32_cache", {})
-    hit = cache.get(slot)
+def cached(owner, slot: str, sources, build):
+    """``build(*sources)`` (run under ``torch.no_grad()``) cached in ``owner.__dict__[slot]``
+    (``owner`` a module) and rebuilt when one of the ``sources`` (parameters, or None) changes:
+    its data pointer, version, dtype or device."""
+    key = tuple([None if p is None else (p.data_ptr(), p._version, p.dtype, p.device)
+                 for p in sources])  # a list first: cheaper than a generator on the eager path
+    hit = owner.__dict__.get(slot)
     if hit is None or hit[0] != key:
         with torch.no_grad():
-            hit = (key, f32c(t))
-        cache[slot] = hit
+            hit = (key, build(*sources))
+        owner.__dict__[slot] = hit
     return hit[1]
+
+
+def f32_cached(owner, t: Optional[Tensor], slot: str) -> Optional[Tensor]:
+    """fp32 contiguous copy of a small parameter cached on ``owner`` (:func:`cached`)."""
+    return None if t is None else cached(owner, "_vm_f32_" + slot, (t,), f32c)
+
+
+def strides2(t: Optional[Tensor]) -> Tuple[int, int]:
+    """The first two element strides of an optional tensor, zeros for None."""
+    return (0, 0) if t is None else (t.stride(0), t.stride(1))
+
+
+def strides3(t: Optional[Tensor]) -> Tuple[int, int, int]:
+    """The three element strides of an optional (b, d, l) tensor, zeros for None."""
+    return (0, 0, 0) if t is None else (t.stride(0), t.stride(1), t.stride(2))
+
+
+def dtype_code_of(t: Optional[Tensor]) -> int:
+    """The ABI's dtype code of an optional tensor, 0 for None."""
+    return 0 if t is None else dtype_code(t.dtype)
+
+
+def _needs_grad(*tensors: Optional[Tensor]) -> bool:
+    """Whether a call over these operands has to build an autograd graph."""
+    return torch.is_grad_enabled() and any(t is not None and t.requires_grad for t in tensors)
 
 
 def _lastdim_contig(t: Optional[Tensor]) -> Optional[Tensor]:
@@ -114,91 +138,88 @@ class _Slot(threading.local):
     value = None
 
 
-_WORKSPACE = {}
-_WS_OVERRIDE = _Slot()
+class _Override:
+    """:meth:`_Buffers.override`: entered, ``buf`` takes this thread's slot of ``kind`` (and is
+    remembered where the kind remembers); left, the slot's previous value comes back."""
 
-
-class scratch_override:
-    """Within the block every kernel that needs scratch (the segmented token-major scan,
-    the channel-major conv_proj's x_proj partials) uses ``buf`` (a uint8 device tensor owned
-    by the caller) instead of the per-stream cache — how a captured HIP graph keeps its
-    scratch alive and fixed for its lifetime (graphs.StreamingChunkGraph).  Consumers run
-    one after another on one stream, so they share the buffer from offset 0."""
-
-    def __init__(self, buf: Tensor):
-        self.buf = buf
+    def __init__(self, kind: "_Buffers", buf: Tensor):
+        self.kind, self.buf = kind, buf
 
     def __enter__(self):
-        self.prev = _WS_OVERRIDE.value
-        _WS_OVERRIDE.value = self.buf
+        kind = self.kind
+        self.prev, kind.slot.value = kind.slot.value, self.buf
+        if kind.seen is not None:
+            kind.seen[id(self.buf)] = self.buf
         return self.buf
 
     def __exit__(self, *exc):
-        _WS_OVERRIDE.value = self.prev
+        self.kind.slot.value = self.prev
         return False
 
 
-def scratch(device: torch.device, stream: int, nbytes: int) -> Optional[Tensor]:
-    """Kernel scratch, one buffer per (device, stream), grown and never shrunk (or the
-    caller's buffer inside ``scratch_override``).  When it grows, the old buffer is released
-    back to the caching allocator on that same stream, so work already queued there
-    finishes first.  Captured HIP graphs own their scratch (graphs.StreamingChunkGraph) and
-    never reach this cache."""
-    if nbytes <= 0:
-        return None
-    ov = _WS_OVERRIDE.value
-    if ov is not None:
-        if ov.numel() < nbytes:
-            raise RuntimeError(f"scratch_override buffer too small: {ov.numel()} < {nbytes}")
-        return ov
-    key = (device.type, device.index, stream)
-    buf = _WORKSPACE.get(key)
-    if buf is None or buf.numel() < nbytes:
-        buf = torch.empty(nbytes, dtype=torch.uint8, device=device)
-        _WORKSPACE[key] = buf
-    return buf
+class _Buffers:
+    """One kind of per-stream device buffer: a cache keyed by (device type, device index,
+    stream), grown by replacing the buffer and never shrunk, and a per-host-thread override
+    (:meth:`override`) that puts a caller-owned buffer in its place — how a captured HIP graph
+    keeps its buffers alive and fixed for its lifetime (graphs.StreamingChunkGraph).  The
+    kinds differ only in what the constructor names: ``zeroed`` (the fill of a new buffer),
+    ``floor`` (its least size), ``empty_is_none`` (a request of no bytes gets no buffer),
+    ``small_override_raises`` (an override below the request raises, else gets no buffer) and
+    ``remember`` (overrides are kept, weakly, for :meth:`used`)."""
+
+    def __init__(self, name: str, *, zeroed: bool, floor: int = 0, empty_is_none: bool = True,
+                 small_override_raises: bool = True, remember: bool = False):
+        self.name, self.floor, self.empty_is_none = name, floor, empty_is_none
+        self.small_override_raises = small_override_raises
+        self.alloc = torch.zeros if zeroed else torch.empty
+        self.cache = {}
+        self.slot = _Slot()
+        self.seen = weakref.WeakValueDictionary() if remember else None  # id -> override buffer
+
+    def override(self, buf: Tensor):
+        """A context manager: within the block :meth:`get` on this thread answers ``buf`` (a
+        uint8 device tensor owned by the caller) instead of the per-stream buffer."""
+        return _Override(self, buf)
+
+    def get(self, device: torch.device, stream: int, nbytes: int) -> Optional[Tensor]:
+        if nbytes <= 0 and self.empty_is_none:
+            return None
+        ov = self.slot.value
+        if ov is not None:
+            if ov.numel() >= nbytes:
+                return ov
+            if self.small_override_raises:
+                raise RuntimeError(f"{self.name}_override buffer too small: {ov.numel()} < "
+                                   f"{nbytes}")
+            return None
+        key = (device.type, device.index, stream)
+        buf = self.cache.get(key)
+        if buf is None or buf.numel() < nbytes:
+            buf = self.alloc(max(nbytes, self.floor), dtype=torch.uint8, device=device)
+            self.cache[key] = buf
+        return buf
+
+    def used(self):
+        """Every buffer of this kind the process has used: the per-stream ones and, where
+        remembered, the overrides still alive."""
+        return list(self.cache.values()) + (list(self.seen.values()) if self.seen else [])
 
 
-_SYNC = {}
-_SYNC_OVERRIDE = _Slot()
-_SYNC_SEEN = weakref.WeakValueDictionary()  # id -> caller-owned sync buffer (sync_override)
+# Kernel scratch (the segmented token-major scan, conv_proj's x_proj partials, the backward
+# kernels' partial sums), uninitialised.  When it grows, the old buffer is released back to the
+# caching allocator on that same stream, so work already queued there finishes first.  Consumers
+# run one after another on one stream, so they share the buffer (or the override) from offset
+# 0.  Captured HIP graphs own their scratch and never reach the cache.
+_SCRATCH = _Buffers("scratch", zeroed=False)
+scratch_override, scratch = _SCRATCH.override, _SCRATCH.get
 
-
-class sync_override:
-    """Within the block the one-launch segmented scan uses ``buf`` (a zero-filled uint8
-    device tensor owned by the caller, e.g. a captured graph) as its sync buffer instead of
-    the per-stream one.  The library leaves the buffer zeroed after every launch."""
-
-    def __init__(self, buf: Tensor):
-        self.buf = buf
-
-    def __enter__(self):
-        self.prev = _SYNC_OVERRIDE.value
-        _SYNC_OVERRIDE.value = self.buf
-        _SYNC_SEEN[id(self.buf)] = self.buf
-        return self.buf
-
-    def __exit__(self, *exc):
-        _SYNC_OVERRIDE.value = self.prev
-        return False
-
-
-def sync_buffer(device: torch.device, stream: int, nbytes: int) -> Optional[Tensor]:
-    """The one-launch scan's sync buffer: zero-filled when allocated, left valid for the next
-    launch by every launch (epoch-tagged hand-off granules, ABI v9), one per (device, stream)
-    so no two concurrent launches share it; grown (a new zeroed buffer) when a shape needs
-    more."""
-    if nbytes <= 0:
-        return None
-    ov = _SYNC_OVERRIDE.value
-    if ov is not None:
-        return ov if ov.numel() >= nbytes else None
-    key = (device.type, device.index, stream)
-    buf = _SYNC.get(key)
-    if buf is None or buf.numel() < nbytes:
-        buf = torch.zeros(max(nbytes, 4096), dtype=torch.uint8, device=device)
-        _SYNC[key] = buf
-    return buf
+# The one-launch segmented scan's sync buffer: zero-filled when allocated (the override too, by
+# its owner), left valid for the next launch by every launch (epoch-tagged hand-off granules,
+# ABI v9), one per (device, stream) so no two concurrent launches share it; grown (a new zeroed
+# buffer) when a shape needs more.  An override too small for a shape gets no buffer: the scan
+# then runs its two-launch form.
+_SYNC = _Buffers("sync", zeroed=True, floor=4096, small_override_raises=False, remember=True)
+sync_override, sync_buffer = _SYNC.override, _SYNC.get
 
 
 SYNC_HEADER_BYTES = 16  # error word, epoch, start count, pad (ABI v9)
@@ -232,7 +253,7 @@ def check_scan_sync(clear: bool = True) -> None:
     kernels never hang and never write plausible wrong values on a timeout (the affected
     outputs are NaN); this turns the event into an exception."""
     bad = 0
-    for buf in list(_SYNC.values()) + list(_SYNC_SEEN.values()):
+    for buf in _SYNC.used():
         if scan_sync_status(buf):
             bad += 1
             if clear:
@@ -254,25 +275,31 @@ def scan_workspace_bytes(batch: int, dim: int, seqlen: int, dstate: int,
     return int(_lib.load().vm_selective_scan_workspace_bytes(batch, dim, seqlen, dstate, seg))
 
 
+def _workspace(device, stream, nbytes: int, given: Optional[Tensor], what: str):
+    """The ``nbytes`` of workspace a launch needs (None for 0): ``given``, the caller's uint8
+    device buffer (ValueError where it is too small), else the per-stream scratch."""
+    if not nbytes:
+        return None
+    if given is None:
+        return scratch(device, int(stream), nbytes)
+    if given.numel() < nbytes:
+        raise ValueError(f"{what} workspace too small: {given.numel()} < {nbytes}")
+    return given
+
+
 def _scan_buffers(device, stream, batch, dim, seqlen, dstate, workspace: Optional[Tensor]):
     """``(seg, ws, ws_bytes, sync, sync_bytes)`` of a token-major scan launch: the segment
     option, the workspace the library asks for (``workspace`` or the per-stream scratch) and,
     for a segmented scan under ``scan_one_launch``, the sync buffer."""
     seg = int(options.get().scan_segments)
     ws_bytes = scan_workspace_bytes(batch, dim, seqlen, dstate, seg)
-    ws, sync, sync_bytes = None, None, 0
-    if ws_bytes:
-        if workspace is not None:
-            if workspace.numel() < ws_bytes:
-                raise ValueError(f"scan workspace too small: {workspace.numel()} < {ws_bytes}")
-            ws = workspace
-        else:
-            ws = scratch(device, int(stream), ws_bytes)
-        if options.get().scan_one_launch:
-            sync_bytes = scan_sync_bytes(batch, dim, seqlen, dstate, seg)
-            sync = sync_buffer(device, int(stream), sync_bytes)
-            if sync is None:
-                sync_bytes = 0
+    ws = _workspace(device, stream, ws_bytes, workspace, "scan")
+    sync, sync_bytes = None, 0
+    if ws_bytes and options.get().scan_one_launch:
+        sync_bytes = scan_sync_bytes(batch, dim, seqlen, dstate, seg)
+        sync = sync_buffer(device, int(stream), sync_bytes)
+        if sync is None:
+            sync_bytes = 0
     return seg, ws, ws_bytes, sync, sync_bytes
 
 
@@ -292,9 +319,9 @@ def scan_raw(u, u_s, delta, dl_s, A32, B, b_s, C, c_s, D32, z, z_s, bias32, soft
     args = (_p(u), u_s[0], u_s[1], u_s[2], _p(delta), dl_s[0], dl_s[1], dl_s[2], _p(A32),
             _p(B), b_s[0], b_s[1], b_s[2], _p(C), c_s[0], c_s[1], c_s[2],
             _p(D32), _p(z), z_s[0], z_s[1], z_s[2], _p(bias32), int(softplus),
-            _p(h0), dtype_code(h0.dtype) if h0 is not None else 0, h0_s[0], h0_s[1],
-            _p(h_last), dtype_code(h_last.dtype) if h_last is not None else 0, hl_s[0],
-            hl_s[1], _p(out), o_s[0], o_s[1], o_s[2], out_len, batch, dim, seqlen, dstate, dtype)
+            _p(h0), dtype_code_of(h0), h0_s[0], h0_s[1],
+            _p(h_last), dtype_code_of(h_last), hl_s[0], hl_s[1],
+            _p(out), o_s[0], o_s[1], o_s[2], out_len, batch, dim, seqlen, dstate, dtype)
     if pair is None:
         rc = lib.vm_selective_scan_fwd(*args, seg, _p(ws), ws_bytes, _p(sync), sync_bytes,
                                        stream)
@@ -324,23 +351,14 @@ def selective_scan_bwd_raw(u, u_s, delta, dl_s, A32, B, b_s, C, c_s, D32, z, z_s
     dh0 fp32.  ``workspace`` (a uint8 device buffer) replaces the per-stream scratch."""
     lib = _lib.load()
     ws_bytes = scan_bwd_workspace_bytes(batch, dim, seqlen, dstate)
-    ws = None
-    if ws_bytes:
-        if workspace is not None:
-            if workspace.numel() < ws_bytes:
-                raise ValueError(f"scan backward workspace too small: {workspace.numel()} < "
-                                 f"{ws_bytes}")
-            ws = workspace
-        else:
-            ws = scratch(u.device, int(stream), ws_bytes)
-    s2 = lambda s: (s[0], s[1])  # noqa: E731
+    ws = _workspace(u.device, stream, ws_bytes, workspace, "scan backward")
     rc = lib.vm_selective_scan_bwd(
         _p(u), *u_s, _p(delta), *dl_s, _p(A32), _p(B), *b_s, _p(C), *c_s,
         _p(D32), _p(z), *z_s, _p(bias32), int(softplus),
-        _p(h0), dtype_code(h0.dtype) if h0 is not None else 0, *s2(h0_s),
-        _p(dout), *do_s, _p(dh_last), *s2(dhl_s),
+        _p(h0), dtype_code_of(h0), *h0_s[:2],
+        _p(dout), *do_s, _p(dh_last), *dhl_s[:2],
         _p(du), *du_s, _p(ddelta), *dd_s, _p(dz), *dz_s, _p(dB), *dB_s, _p(dC), *dC_s,
-        _p(dA), _p(dD), _p(dbias), _p(dh0), *s2(dh0_s),
+        _p(dA), _p(dD), _p(dbias), _p(dh0), *dh0_s[:2],
         batch, dim, seqlen, dstate, dtype, _p(ws), ws_bytes, stream)
     _lib.check(rc, "vm_selective_scan_bwd")
 
@@ -402,8 +420,8 @@ def scan_dtproj_raw(u, u_s, dtl, dtl_s, dt_rank, wdt_pad, A32, B, b_s, C, c_s, D
         _p(wdt_pad), wdt_pad.stride(0), _p(A32),
         _p(B), b_s[0], b_s[1], b_s[2], _p(C), c_s[0], c_s[1], c_s[2],
         _p(D32), _p(z), z_s[0], z_s[1], z_s[2], _p(bias32), 1,
-        _p(h0), dtype_code(h0.dtype) if h0 is not None else 0, h0_s[0], h0_s[1],
-        _p(h_last), dtype_code(h_last.dtype) if h_last is not None else 0, hl_s[0], hl_s[1],
+        _p(h0), dtype_code_of(h0), h0_s[0], h0_s[1],
+        _p(h_last), dtype_code_of(h_last), hl_s[0], hl_s[1],
         _p(out), o_s[0], o_s[1], o_s[2], out_len, batch, dim, seqlen, dstate,
         dtype_code(u.dtype), seg, _p(ws), ws_bytes, _p(sync), sync_bytes, stream)
     _lib.check(rc, "vm_selective_scan_dtproj_fwd")
@@ -415,24 +433,14 @@ def conv_raw(x, x_s, w32, b32, cs_in, csi_s, cs_out, cso_s, out, o_s, out_len, b
     lib = _lib.load()
     rc = lib.vm_causal_conv1d_fwd(
         _p(x), x_s[0], x_s[1], x_s[2], _p(w32), _p(b32),
-        _p(cs_in), dtype_code(cs_in.dtype) if cs_in is not None else 0, csi_s[0], csi_s[1],
-        _p(cs_out), dtype_code(cs_out.dtype) if cs_out is not None else 0, cso_s[0], cso_s[1],
+        _p(cs_in), dtype_code_of(cs_in), csi_s[0], csi_s[1],
+        _p(cs_out), dtype_code_of(cs_out), cso_s[0], cso_s[1],
         _p(out), o_s[0], o_s[1], o_s[2], out_len, batch, dim, seqlen, width, int(silu), dtype,
         stream)
     _lib.check(rc, "vm_causal_conv1d_fwd")
 
 
 CONV_BWD_MAX_WIDTH = 4  # the taps vm_causal_conv1d_bwd takes (vm_conv_bwd_plan.h kCbWM)
-
-
-def _bwd_workspace(device, stream, ws_bytes: int, workspace: Optional[Tensor], what: str):
-    if not ws_bytes:
-        return None
-    if workspace is None:
-        return scratch(device, int(stream), ws_bytes)
-    if workspace.numel() < ws_bytes:
-        raise ValueError(f"{what} workspace too small: {workspace.numel()} < {ws_bytes}")
-    return workspace
 
 
 def conv_bwd_workspace_bytes(batch: int, dim: int, seqlen: int, width: int) -> int:
@@ -449,10 +457,9 @@ def conv_bwd_raw(x, x_s, w32, b32, cs_in, csi_s, dout, do_s, dx, dx_s, dcs, dcs_
     ``workspace`` (a uint8 device buffer) replaces the per-stream scratch."""
     lib = _lib.load()
     ws_bytes = conv_bwd_workspace_bytes(batch, dim, seqlen, width)
-    ws = _bwd_workspace(x.device, stream, ws_bytes, workspace, "conv backward")
+    ws = _workspace(x.device, stream, ws_bytes, workspace, "conv backward")
     rc = lib.vm_causal_conv1d_bwd(
-        _p(x), *x_s, _p(w32), _p(b32),
-        _p(cs_in), dtype_code(cs_in.dtype) if cs_in is not None else 0, *csi_s,
+        _p(x), *x_s, _p(w32), _p(b32), _p(cs_in), dtype_code_of(cs_in), *csi_s,
         _p(dout), *do_s, _p(dx), *dx_s, _p(dcs), *dcs_s, _p(dw), _p(db),
         batch, dim, seqlen, width, int(silu), dtype, _p(ws), ws_bytes, stream)
     _lib.check(rc, "vm_causal_conv1d_bwd")
@@ -471,11 +478,11 @@ def add_norm_bwd_raw(s, w32, b32, dy, dres_out, dx, dresidual, dw, db, rows, col
     dtype), dw (cols) and db (cols; None iff b32 is None) fp32.  All buffers contiguous."""
     lib = _lib.load()
     ws_bytes = add_norm_bwd_workspace_bytes(rows, cols)
-    ws = _bwd_workspace(s.device, stream, ws_bytes, workspace, "add + norm backward")
+    ws = _workspace(s.device, stream, ws_bytes, workspace, "add + norm backward")
     rc = lib.vm_add_norm_bwd(
         _p(s), dtype_code(s.dtype), _p(w32), _p(b32), _p(dy), dtype_code(dy.dtype),
-        _p(dres_out), _p(dx), dtype_code(dx.dtype), _p(dresidual),
-        dtype_code(dresidual.dtype) if dresidual is not None else 0, _p(dw), _p(db),
+        _p(dres_out), _p(dx), dtype_code(dx.dtype), _p(dresidual), dtype_code_of(dresidual),
+        _p(dw), _p(db),
         rows, cols, float(eps), int(is_rms), _p(ws), ws_bytes, stream)
     _lib.check(rc, "vm_add_norm_bwd")
 
@@ -490,11 +497,11 @@ def conv_proj_raw(xz, xz_s, cw32, cb32, cs_in, csi_s, cs_out, cso_s, wx_pad, e, 
     dt=None skips dt_proj (conv + x_proj only; wdt_pad may be None)."""
     lib = _lib.load()
     nbytes = int(lib.vm_conv_proj_workspace_bytes(batch, out_len, dim, e))
-    ws = scratch(xz.device, int(stream), nbytes)
+    ws = _workspace(xz.device, stream, nbytes, None, "conv_proj")
     rc = lib.vm_conv_proj_fwd(
         _p(xz), xz_s[0], xz_s[1], _p(cw32), _p(cb32),
-        _p(cs_in), dtype_code(cs_in.dtype) if cs_in is not None else 0, csi_s[0], csi_s[1],
-        _p(cs_out), dtype_code(cs_out.dtype) if cs_out is not None else 0, cso_s[0], cso_s[1],
+        _p(cs_in), dtype_code_of(cs_in), csi_s[0], csi_s[1],
+        _p(cs_out), dtype_code_of(cs_out), cso_s[0], cso_s[1],
         _p(wx_pad), e, wx_pad.shape[0], _p(wdt_pad), r,
         wdt_pad.shape[1] if wdt_pad is not None else 0,
         _p(u), u_s[0], u_s[1], _p(xdbl), xd_s[0], xd_s[1], _p(dt),
@@ -520,12 +527,12 @@ def in_proj_conv_proj_raw(hn, w_in, z, cw32, cb32, cs_in, csi_s, cs_out, cso_s, 
     Scratch for the x_proj partials comes from :func:`scratch`."""
     lib = _lib.load()
     nbytes = int(lib.vm_in_proj_conv_proj_workspace_bytes(batch, out_len, dim, e))
-    ws = scratch(hn.device, int(stream), nbytes)
+    ws = _workspace(hn.device, stream, nbytes, None, "in_proj_conv_proj")
     rc = lib.vm_in_proj_conv_proj_fwd(
         _p(hn), hn.stride(0), _p(w_in), w_in.stride(0), hn.shape[1], _p(z), z.stride(0),
         _p(cw32), _p(cb32),
-        _p(cs_in), dtype_code(cs_in.dtype) if cs_in is not None else 0, csi_s[0], csi_s[1],
-        _p(cs_out), dtype_code(cs_out.dtype) if cs_out is not None else 0, cso_s[0], cso_s[1],
+        _p(cs_in), dtype_code_of(cs_in), csi_s[0], csi_s[1],
+        _p(cs_out), dtype_code_of(cs_out), cso_s[0], cso_s[1],
         _p(wx_pad), e, wx_pad.shape[0], _p(wdt_pad if dt is not None else None), r,
         wdt_pad.shape[1] if (wdt_pad is not None and dt is not None) else 0,
         _p(u), u.stride(0), _p(xdbl), xdbl.stride(0), _p(dt),
@@ -539,10 +546,9 @@ def conv_proj_fits(batch: int, out_len: int, seqlen: int, dim: int, e: int, r_pa
     """Whether ``vm_conv_proj_fwd`` accepts this token-major shape (``vm_conv_proj_fits``):
     the wide form (batch > 8) addresses its operands through 31-bit buffer offsets, so very
     long sequences go to the unfused conv + projection path instead of raising."""
-    csi = (cs_in.stride(0), cs_in.stride(1)) if cs_in is not None else (0, 0)
     return bool(_lib.load().vm_conv_proj_fits(
         batch, out_len, seqlen, dim, e, r_pad, 0, xz_s[0], xz_s[1], int(cs_in is not None),
-        dtype_code(cs_in.dtype) if cs_in is not None else 0, csi[0], csi[1], width, u_sl))
+        dtype_code_of(cs_in), *strides2(cs_in), width, u_sl))
 
 
 def conv_proj_workspace_bytes(batch: int, out_len: int, dim: int, e: int) -> int:
@@ -562,11 +568,11 @@ def conv_proj_cm_raw(xz, x_sd, cw32, cb32, cs_in, csi_s, cs_out, cso_s, wx_pad, 
     :func:`scratch`."""
     lib = _lib.load()
     nbytes = conv_proj_cm_workspace_bytes(batch, out_len, dim, e)
-    ws = scratch(xz.device, int(stream), nbytes)
+    ws = _workspace(xz.device, stream, nbytes, None, "conv_proj_cm")
     rc = lib.vm_conv_proj_cm_fwd(
         _p(xz), x_sd, _p(cw32), _p(cb32),
-        _p(cs_in), dtype_code(cs_in.dtype) if cs_in is not None else 0, csi_s[0], csi_s[1],
-        _p(cs_out), dtype_code(cs_out.dtype) if cs_out is not None else 0, cso_s[0], cso_s[1],
+        _p(cs_in), dtype_code_of(cs_in), csi_s[0], csi_s[1],
+        _p(cs_out), dtype_code_of(cs_out), cso_s[0], cso_s[1],
         _p(wx_pad), e, wx_pad.shape[0], _p(wdt_pad), r, wdt_pad.shape[1],
         _p(u), u_sd, _p(xdbl), xd_sd, _p(dt), dt_sd, out_len, batch, dim, seqlen, width,
         _p(ws), nbytes, stream)
@@ -576,11 +582,9 @@ def conv_proj_cm_raw(xz, x_sd, cw32, cb32, cs_in, csi_s, cs_out, cso_s, wx_pad, 
 def add_norm_raw(x, residual, w32, b32, out, residual_out, rows, cols, eps, is_rms, stream):
     lib = _lib.load()
     rc = lib.vm_add_norm_fwd(
-        _p(x), dtype_code(x.dtype), _p(residual),
-        dtype_code(residual.dtype) if residual is not None else 0,
+        _p(x), dtype_code(x.dtype), _p(residual), dtype_code_of(residual),
         _p(w32), _p(b32), _p(out), dtype_code(out.dtype), _p(residual_out),
-        dtype_code(residual_out.dtype) if residual_out is not None else 0,
-        rows, cols, float(eps), int(is_rms), stream)
+        dtype_code_of(residual_out), rows, cols, float(eps), int(is_rms), stream)
     _lib.check(rc, "vm_add_norm_fwd")
 
 
@@ -636,7 +640,7 @@ def linear_wgrad_raw(dy, x, dw, m, n, k, stream, workspace: Optional[Tensor] = N
     overwritten.  ``workspace`` (a uint8 device buffer) replaces the per-stream scratch."""
     lib = _lib.load()
     ws_bytes = linear_wgrad_workspace_bytes(m, n, k)
-    ws = _bwd_workspace(dy.device, stream, ws_bytes, workspace, "linear wgrad")
+    ws = _workspace(dy.device, stream, ws_bytes, workspace, "linear wgrad")
     rc = lib.vm_linear_wgrad(_p(dy), dy.stride(0), _p(x), x.stride(0), _p(dw), dw.stride(0),
                              dtype_code(dw.dtype), m, n, k, dtype_code(x.dtype), _p(ws),
                              ws_bytes if workspace is None else workspace.numel(), stream)
@@ -708,8 +712,8 @@ def linear_fn(x: Tensor, weight: Tensor, bias: Optional[Tensor] = None) -> Tenso
     ``vm_linear_dgrad`` / ``vm_linear_wgrad``.  x and dy are made row-contiguous with torch
     ops where they are not; gradients come back in their inputs' dtypes and shapes, and only
     those that are needed are computed.  Every other case is ``F.linear``."""
-    if (torch.is_grad_enabled() and (x.requires_grad or weight.requires_grad)
-            and options.get().train_gemm == "hip" and _linear_fn_hip_ok(x, weight, bias)):
+    if (_needs_grad(x, weight) and options.get().train_gemm == "hip"
+            and _linear_fn_hip_ok(x, weight, bias)):
         k = weight.shape[1]
         x2 = _rows16(x.reshape(-1, k))
         w = _rows16(weight)
@@ -717,42 +721,10 @@ def linear_fn(x: Tensor, weight: Tensor, bias: Optional[Tensor] = None) -> Tenso
     return torch.nn.functional.linear(x, weight, bias)
 
 
-_CNT = {}
-_CNT_OVERRIDE = _Slot()
-_CNT_SEEN = weakref.WeakValueDictionary()  # id -> caller-owned counter buffer (counter_override)
-
-
-class counter_override:
-    """Within the block ``vm_linear_add_norm_fwd`` takes its hand-off counters from ``buf``
-    (a zero-filled uint8 device tensor owned by the caller, e.g. a captured graph) instead
-    of the per-stream buffer.  The kernel leaves the counters zeroed."""
-
-    def __init__(self, buf: Tensor):
-        self.buf = buf
-
-    def __enter__(self):
-        self.prev = _CNT_OVERRIDE.value
-        _CNT_OVERRIDE.value = self.buf
-        _CNT_SEEN[id(self.buf)] = self.buf
-        return self.buf
-
-    def __exit__(self, *exc):
-        _CNT_OVERRIDE.value = self.prev
-        return False
-
-
-def counter_buffer(device: torch.device, stream: int, nbytes: int) -> Tensor:
-    ov = _CNT_OVERRIDE.value
-    if ov is not None:
-        if ov.numel() < nbytes:
-            raise RuntimeError(f"counter_override buffer too small: {ov.numel()} < {nbytes}")
-        return ov
-    key = (device.type, device.index, stream)
-    buf = _CNT.get(key)
-    if buf is None or buf.numel() < nbytes:
-        buf = torch.zeros(max(nbytes, 4096), dtype=torch.uint8, device=device)
-        _CNT[key] = buf
-    return buf
+# The hand-off counters of vm_linear_add_norm_fwd: zero-filled when allocated (the override
+# too, by its owner, e.g. a captured graph), left zeroed by the kernel.
+_COUNTERS = _Buffers("counter", zeroed=True, floor=4096, empty_is_none=False, remember=True)
+counter_override, counter_buffer = _COUNTERS.override, _COUNTERS.get
 
 
 def linear_add_norm_counter_bytes(m: int) -> int:
@@ -787,7 +759,7 @@ def check_linear_add_norm(clear: bool = True) -> None:
     may still add to it, which would leave a stale count that lets a later launch pass its
     poll early.  The status read synchronises first, so every producer has finished."""
     bad = 0
-    for buf in list(_CNT.values()) + list(_CNT_SEEN.values()):
+    for buf in _COUNTERS.used():
         if linear_add_norm_status(buf):
             bad += 1
             if clear:
@@ -844,12 +816,11 @@ def norm_pool(h: Tensor, residual: Optional[Tensor], rows: int, w32: Tensor,
     ws, nbytes = None, 0
     if sums:
         nbytes = norm_pool_workspace_bytes(Bsz, groups, max_group_rows, C)
-        ws = scratch(h.device, _stream(h), nbytes)
+        ws = _workspace(h.device, _stream(h), nbytes, None, "norm_pool")
     if residual is not None and residual.stride() != h.stride():
         raise ValueError("residual must share h's padded layout")
     rc = _lib.load().vm_norm_pool_fwd(
-        _p(h), dtype_code(h.dtype), _p(residual),
-        dtype_code(residual.dtype) if residual is not None else 0, h.stride(0),
+        _p(h), dtype_code(h.dtype), _p(residual), dtype_code_of(residual), h.stride(0),
         _p(w32), _p(b32), float(eps), int(is_rms), _p(out), dtype_code(out.dtype),
         out.stride(0), Bsz, rows, C, head, groups, group_rows, _p(bounds), max_group_rows,
         int(rev_frame), _p(ws), nbytes, _stream(h))
@@ -882,9 +853,11 @@ def pool_finish(ws: Optional[Tensor], feats: Tensor, *, mode: str, keep_temporal
 BWD_DSTATE = 16  # the state count vm_selective_scan_bwd takes
 
 
-def _tm_strides(t: Tensor) -> Tuple[int, int, int]:
-    """(batch, channel|state, step) element strides of a token-major (b, d, l) view; a
-    single channel's stride is immaterial and reported as 1."""
+def _tm_strides(t: Optional[Tensor]) -> Tuple[int, int, int]:
+    """(batch, channel|state, step) element strides of a token-major (b, d, l) view (zeros
+    for None); a single channel's stride is immaterial and reported as 1."""
+    if t is None:
+        return (0, 0, 0)
     return (t.stride(0), 1 if t.shape[1] <= 1 else t.stride(1), t.stride(2))
 
 
@@ -922,8 +895,7 @@ class _SelectiveScan(torch.autograd.Function):
         dD = f32(dim) if D is not None else None
         dbias = f32(dim) if bias is not None else None
         dh0 = f32(batch, dim, n) if h0 is not None else None
-        s3 = lambda t: _tm_strides(t) if t is not None else (0, 0, 0)  # noqa: E731
-        s2 = lambda t: (t.stride(0), t.stride(1)) if t is not None else (0, 0)  # noqa: E731
+        s3, s2 = _tm_strides, strides2
         selective_scan_bwd_raw(u, s3(u), delta, s3(delta), A, B, s3(B), C, s3(C), D, z, s3(z),
                                bias, ctx.softplus, h0, s2(h0), dout, s3(dout), dh_last,
                                s2(dh_last), du, s3(du), ddelta, s3(ddelta), dz, s3(dz),
@@ -984,9 +956,7 @@ def selective_scan_fn(u: Tensor, delta: Tensor, A: Tensor, B: Tensor, C: Tensor,
             last_state_out.copy_(h)
             h = last_state_out
         return out, h
-    if torch.is_grad_enabled() and any(
-            t is not None and t.requires_grad
-            for t in (u, delta, A, B, C, D, z, delta_bias, initial_state)):
+    if _needs_grad(u, delta, A, B, C, D, z, delta_bias, initial_state):
         return _selective_scan_autograd(u, delta, A, B, C, D, z, delta_bias, delta_softplus,
                                         return_last_state, initial_state, last_state_out)
     # Layout follows u: token-major views (unit channel stride, e.g. a transposed
@@ -1015,12 +985,9 @@ def selective_scan_fn(u: Tensor, delta: Tensor, A: Tensor, B: Tensor, C: Tensor,
             (batch, dim, dstate), dtype=torch.float32, device=u.device)
         if hl.stride(-1) != 1:
             raise ValueError("last_state_out must have unit stride on the state axis")
-    s3 = lambda t: (t.stride(0), t.stride(1), t.stride(2))  # noqa: E731
-    scan_raw(u, s3(u), delta, s3(delta), f32c(A), B, s3(B), C, s3(C),
-             f32c(D), z, s3(z) if z is not None else (0, 0, 0),
-             f32c(delta_bias), delta_softplus,
-             h0, (h0.stride(0), h0.stride(1)) if h0 is not None else (0, 0),
-             hl, (hl.stride(0), hl.stride(1)) if hl is not None else (0, 0),
+    s3 = strides3
+    scan_raw(u, s3(u), delta, s3(delta), f32c(A), B, s3(B), C, s3(C), f32c(D), z, s3(z),
+             f32c(delta_bias), delta_softplus, h0, strides2(h0), hl, strides2(hl),
              out, s3(out), seqlen, batch, dim, seqlen, dstate, dt, _stream(u))
     return (out, hl) if return_last_state else out
 
@@ -1080,9 +1047,8 @@ class _CausalConv1d(torch.autograd.Function):
         dcs = None
         if cs is not None and ctx.needs_input_grad[3]:
             dcs = torch.empty((batch, dim, width), dtype=torch.float32, device=dev)
-        s2 = lambda t: (t.stride(0), t.stride(1)) if t is not None else (0, 0)  # noqa: E731
-        conv_bwd_raw(x, _tm_strides(x), w, b, cs, s2(cs), dout, _tm_strides(dout), dx,
-                     _tm_strides(dx), dcs, s2(dcs), dw, db, batch, dim, seqlen, width,
+        conv_bwd_raw(x, _tm_strides(x), w, b, cs, strides2(cs), dout, _tm_strides(dout), dx,
+                     _tm_strides(dx), dcs, strides2(dcs), dw, db, batch, dim, seqlen, width,
                      ctx.silu, dtype_code(x.dtype), _stream(x))
         return dx, dw, db, None if dcs is None else dcs.to(cs.dtype), None
 
@@ -1125,8 +1091,7 @@ def causal_conv1d_fn(x: Tensor, weight: Tensor, bias: Optional[Tensor] = None,
         weight = weight.reshape(weight.shape[0], weight.shape[-1])
     batch, dim, seqlen = x.shape
     width = weight.shape[1]
-    if torch.is_grad_enabled() and any(
-            t is not None and t.requires_grad for t in (x, weight, bias, conv_state)):
+    if _needs_grad(x, weight, bias, conv_state):
         return _causal_conv1d_autograd(x, weight, bias, activation, conv_state,
                                        return_conv_state)
     tm = dim > 1 and x.stride(1) == 1  # token-major view: keep the layout
@@ -1140,10 +1105,8 @@ def causal_conv1d_fn(x: Tensor, weight: Tensor, bias: Optional[Tensor] = None,
     if return_conv_state:
         cs_dtype = conv_state.dtype if conv_state is not None else x.dtype
         cs_out = torch.empty((batch, dim, width), dtype=cs_dtype, device=x.device)
-    conv_raw(x, (x.stride(0), x.stride(1), x.stride(2)), f32c(weight), f32c(bias),
-             cs_in, (cs_in.stride(0), cs_in.stride(1)) if cs_in is not None else (0, 0),
-             cs_out, (cs_out.stride(0), cs_out.stride(1)) if cs_out is not None else (0, 0),
-             out, (out.stride(0), out.stride(1), out.stride(2)), seqlen, batch, dim, seqlen, width,
+    conv_raw(x, strides3(x), f32c(weight), f32c(bias), cs_in, strides2(cs_in), cs_out,
+             strides2(cs_out), out, strides3(out), seqlen, batch, dim, seqlen, width,
              activation is not None, dtype_code(x.dtype), _stream(x))
     return (out, cs_out) if return_conv_state else out
 
@@ -1251,8 +1214,7 @@ def _norm_torch_ops(x, weight, bias, residual, prenorm, residual_in_fp32, eps, i
 def _norm(x, weight, bias, residual, prenorm, residual_in_fp32, eps, is_rms, out=None,
           residual_out=None, owner=None):
     require_gpu(x, weight, bias, residual, what="rms_norm_fn/layer_norm_fn")
-    if torch.is_grad_enabled() and any(
-            t is not None and t.requires_grad for t in (x, residual, weight, bias)):
+    if _needs_grad(x, residual, weight, bias):
         if out is not None or residual_out is not None:
             raise ValueError("rms_norm_fn/layer_norm_fn: out= / residual_out= write in place, "
                              "which has no gradient; drop them or call under torch.no_grad()")

@@ -188,6 +188,22 @@ def mixer_layout(batch: int, d_inner: int, device: torch.device) -> str:
     return "tm"
 
 
+def _fp32_copies(A_log, D, dt_bias, conv_w, conv_b):
+    """What :meth:`Mamba._fp32_params` caches, from the parameters themselves."""
+    return ((-torch.exp(A_log.float())).contiguous(), K.f32c(D), K.f32c(dt_bias),
+            K.f32c(conv_w.reshape(conv_w.shape[0], conv_w.shape[-1])), K.f32c(conv_b))
+
+
+def _padded_copies(wx, wdt):
+    """What :meth:`Mamba._padded_proj_weights` caches, from the two weights."""
+    e, r = wx.shape[0], wdt.shape[1]
+    wx_pad = wx.new_zeros(((e + 15) // 16 * 16, wx.shape[1]))
+    wx_pad[:e] = wx
+    wdt_pad = wdt.new_zeros((wdt.shape[0], 32 if r <= 32 else 64))
+    wdt_pad[:, :r] = wdt
+    return wx_pad.contiguous(), wdt_pad.contiguous()
+
+
 class InferenceParamsLike(Protocol):
     seqlen_offset: int
     key_value_memory_dict: MutableMapping[int, Tuple[Tensor, Tensor]]
@@ -244,43 +260,24 @@ class Mamba(nn.Module):
         self.D = nn.Parameter(torch.ones(self.d_inner, device=device))
         self.D._no_weight_decay = True
         self.out_proj = nn.Linear(self.d_inner, d_model, bias=bias, **fk)
-        self._pcache_key = None
-        self._pcache = None
 
     # ------------------------------------------------------------------ params (fp32)
     def _fp32_params(self):
         """A = -exp(A_log), D, dt bias, conv weight/bias as fp32 contiguous (cached per
         parameter version so bf16 models convert once, not per call)."""
-        srcs = (self.A_log, self.D, self.dt_proj.bias, self.conv1d.weight, self.conv1d.bias)
-        key = tuple(None if p is None else (p.data_ptr(), p._version, p.dtype, p.device)
-                    for p in srcs)
-        if key != self._pcache_key:
-            with torch.no_grad():
-                A = (-torch.exp(self.A_log.float())).contiguous()
-                Dv = K.f32c(self.D)
-                bias = K.f32c(self.dt_proj.bias)
-                w = K.f32c(self.conv1d.weight.reshape(self.d_inner, self.d_conv))
-                cb = K.f32c(self.conv1d.bias)
-            self._pcache = (A, Dv, bias, w, cb)
-            self._pcache_key = key
-        return self._pcache
+        return K.cached(self, "_pcache", (self.A_log, self.D, self.dt_proj.bias,
+                                          self.conv1d.weight, self.conv1d.bias), _fp32_copies)
 
     def _padded_proj_weights(self):
         """x_proj / dt_proj weights zero-padded for the fused conv_proj kernel:
         W_x -> (round_up(R+2N, 16), D), W_dt -> (D, 32 or 64); cached per version."""
-        srcs = (self.x_proj.weight, self.dt_proj.weight)
-        key = tuple((p.data_ptr(), p._version, p.dtype, p.device) for p in srcs)
-        if key != getattr(self, "_wpad_key", None):
-            with torch.no_grad():
-                wx, wdt = self.x_proj.weight, self.dt_proj.weight
-                e, r = wx.shape[0], wdt.shape[1]
-                wx_pad = wx.new_zeros(((e + 15) // 16 * 16, wx.shape[1]))
-                wx_pad[:e] = wx
-                wdt_pad = wdt.new_zeros((wdt.shape[0], 32 if r <= 32 else 64))
-                wdt_pad[:, :r] = wdt
-            self._wpad = (wx_pad.contiguous(), wdt_pad.contiguous())
-            self._wpad_key = key
-        return self._wpad
+        return K.cached(self, "_wpad", (self.x_proj.weight, self.dt_proj.weight), _padded_copies)
+
+    def _tm_strides(self, Lp: int):
+        """(batch, channel, step) element strides of the token-major buffers of ``Lp`` padded
+        tokens per clip: u / dt / y (n, D), xz (n, 2D) and the B / C columns of x_dbl (n, E)."""
+        Dm, E = self.d_inner, self.dt_rank + 2 * self.d_state
+        return (Lp * Dm, 1, Dm), (Lp * 2 * Dm, 1, 2 * Dm), (Lp * E, 1, E)
 
     def _fused_conv_proj_ok(self, hn: Tensor, seqlen: int, conv_state_in: Optional[Tensor] = None,
                             tm: bool = True) -> bool:
@@ -328,10 +325,7 @@ class Mamba(nn.Module):
             xz += self.in_proj.bias.to(xz.dtype)[:, None]
         x, z = xz[:Dm], xz[Dm:]
         u = torch.empty((Dm, n), dtype=hn.dtype, device=hn.device)
-        csi_s = ((conv_state_in.stride(0), conv_state_in.stride(1))
-                 if conv_state_in is not None else (0, 0))
-        cso_s = ((conv_state_out.stride(0), conv_state_out.stride(1))
-                 if conv_state_out is not None else (0, 0))
+        csi_s, cso_s = K.strides2(conv_state_in), K.strides2(conv_state_out)
         if self._fused_conv_proj_ok(hn, seqlen, tm=False):
             # conv + silu -> x_proj -> dt_proj with a fixed reduction order
             # (vm_conv_proj_cm.hip): faster than the latency-bound library GEMMs at small
@@ -350,9 +344,7 @@ class Mamba(nn.Module):
             dt = _matmul(self.dt_proj.weight, x_dbl[:R])  # (D, B*Lp), bias added in scan
         y = torch.empty_like(u)
         K.scan_raw(u, rows3, dt, rows3, A, x_dbl[R:R + N], rows3, x_dbl[R + N:], rows3, Dv,
-                   z, rows3, dbias, True,
-                   h0, (h0.stride(0), h0.stride(1)) if h0 is not None else (0, 0),
-                   h_last, (h_last.stride(0), h_last.stride(1)) if h_last is not None else (0, 0),
+                   z, rows3, dbias, True, h0, K.strides2(h0), h_last, K.strides2(h_last),
                    y, rows3, Lp, Bsz, Dm, seqlen, N, dt_code, stream)
         out = _matmul(y.t(), self.out_proj.weight.t())  # (B*Lp, C)
         if self.out_proj.bias is not None:
@@ -383,19 +375,22 @@ class Mamba(nn.Module):
             return fits != 0
         return fits == 3 or (fits == 1 and Bsz > K.CONV_PROJ_SMALL_MAX_BATCH)
 
-    def _tm_front(self, hn, seqlen, conv_state_in, conv_state_out, bufs=None, want_dt=True):
+    def _tm_front(self, hn, seqlen, conv_state_in, conv_state_out, cw, cb, bufs=None,
+                  want_dt=True):
         """in_proj -> conv + silu -> x_proj -> dt_proj of the token-major form: (xz, u,
-        x_dbl, dt), each (B*Lp, channels).  ``bufs`` = preallocated (xz, u, x_dbl, dt) (the
-        refiner's paired buffers); otherwise they are allocated here.  ``want_dt=False``
-        (fused conv_proj only) skips dt_proj: dt is None, the scan computes it."""
+        x_dbl, dt), each (B*Lp, channels).  ``cw`` / ``cb`` = the fp32 conv weight / bias of
+        the caller's :meth:`_fp32_params` (one cache check per forward, not two).  ``bufs`` =
+        preallocated (xz, u, x_dbl, dt) (the refiner's paired buffers); otherwise they are
+        allocated here.  ``want_dt=False`` (fused conv_proj only) skips dt_proj: dt is None,
+        the scan computes it."""
         Bsz, Lp, C = hn.shape
         Dm, N, R, W = self.d_inner, self.d_state, self.dt_rank, self.d_conv
         n = Bsz * Lp
         E = R + 2 * N
         dt_code = K.dtype_code(hn.dtype)
         stream = torch.cuda.current_stream(hn.device).cuda_stream
-        _, _, _, cw, cb = self._fp32_params()
-        s_u, s_xz = (Lp * Dm, 1, Dm), (Lp * 2 * Dm, 1, 2 * Dm)
+        s_u, s_xz, _ = self._tm_strides(Lp)
+        csi_s, cso_s = K.strides2(conv_state_in), K.strides2(conv_state_out)
         z_side = None
         if bufs is None and self._in_proj_conv_ok(hn, seqlen, want_dt):
             # in_proj with the conv + SiLU and the x_proj split partials in its epilogue
@@ -406,10 +401,6 @@ class Mamba(nn.Module):
             u = torch.empty((n, Dm), dtype=hn.dtype, device=hn.device)
             x_dbl = torch.empty((n, E), dtype=hn.dtype, device=hn.device)
             dt = torch.empty((n, Dm), dtype=hn.dtype, device=hn.device) if want_dt else None
-            csi_s = ((conv_state_in.stride(0), conv_state_in.stride(1))
-                     if conv_state_in is not None else (0, 0))
-            cso_s = ((conv_state_out.stride(0), conv_state_out.stride(1))
-                     if conv_state_out is not None else (0, 0))
             K.in_proj_conv_proj_raw(hn.view(n, C), self.in_proj.weight, xz[:, Dm:], cw, cb,
                                     conv_state_in, csi_s, conv_state_out, cso_s, wx_pad, E,
                                     wdt_pad, R, u, x_dbl, dt, Lp, Bsz, Dm, seqlen, W, stream)
@@ -438,10 +429,6 @@ class Mamba(nn.Module):
         else:
             xz, u, x_dbl, dt = bufs
             _linear_into(hn.view(n, C), self.in_proj.weight, self.in_proj.bias, xz, clips=Bsz)
-        csi_s = ((conv_state_in.stride(0), conv_state_in.stride(1))
-                 if conv_state_in is not None else (0, 0))
-        cso_s = ((conv_state_out.stride(0), conv_state_out.stride(1))
-                 if conv_state_out is not None else (0, 0))
         if self._fused_conv_proj_ok(hn, seqlen, conv_state_in):
             # conv + silu -> x_proj -> dt_proj in one kernel (vm_conv_proj.hip).  The scan
             # keeps the delta activation softplus(dt + bias): moved into conv_proj's dt
@@ -508,15 +495,14 @@ class Mamba(nn.Module):
         E = R + 2 * N
         dt_code = K.dtype_code(hn.dtype)
         stream = torch.cuda.current_stream(hn.device).cuda_stream
-        A, Dv, dbias, _, _ = self._fp32_params()
-        s_u, s_xz, s_bc = (Lp * Dm, 1, Dm), (Lp * 2 * Dm, 1, 2 * Dm), (Lp * E, 1, E)
+        A, Dv, dbias, cw, cb = self._fp32_params()
+        s_u, s_xz, s_bc = self._tm_strides(Lp)
         dtp = self._dtp_ok(hn, seqlen, conv_state_in)
-        xz, u, x_dbl, dt = self._tm_front(hn, seqlen, conv_state_in, conv_state_out,
+        xz, u, x_dbl, dt = self._tm_front(hn, seqlen, conv_state_in, conv_state_out, cw, cb,
                                           want_dt=not dtp)
         _phase.pre_done(self.layer_idx)  # sub-batch streams: the next part's pre phase may go
         y = torch.empty_like(u)
-        h0_s = (h0.stride(0), h0.stride(1)) if h0 is not None else (0, 0)
-        hl_s = (h_last.stride(0), h_last.stride(1)) if h_last is not None else (0, 0)
+        h0_s, hl_s = K.strides2(h0), K.strides2(h_last)
         log = _SCAN_EVENTS[0]
         ev0 = _scan_event(log)
         if dtp:  # dt_proj inside the scan: no dt rows written or read

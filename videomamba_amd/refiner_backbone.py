@@ -161,23 +161,23 @@ class BiMambaRefinerBlock(nn.Module):
         dt = torch.empty((2 * n, Dm), dtype=hdt, device=dev)
         half = lambda t, i: t[i * n:(i + 1) * n]  # noqa: E731
         conv_new = torch.empty((B, Dm, W), dtype=st_f[0].dtype, device=dev)
-        mf._tm_front(hn[:B], L, st_f[0], conv_new,
+        A_f, D_f, bias_f, cw_f, cb_f = mf._fp32_params()
+        A_b, D_b, bias_b, cw_b, cb_b = mb._fp32_params()
+        mf._tm_front(hn[:B], L, st_f[0], conv_new, cw_f, cb_f,
                      bufs=tuple(half(t, 0) for t in (xz, u, x_dbl, dt)))
-        mb._tm_front(hn[B:], L, st_b[0], None,
+        mb._tm_front(hn[B:], L, st_b[0], None, cw_b, cb_b,
                      bufs=tuple(half(t, 1) for t in (xz, u, x_dbl, dt)))
 
         # one scan for both directions; both ssm states update in place (the reference's
         # aliasing), the backward one through a buffer of the forward one's layout if needed
-        A_f, D_f, bias_f, _, _ = mf._fp32_params()
-        A_b, D_b, bias_b, _, _ = mb._fp32_params()
         ssm_f, ssm_b = st_f[1], st_b[1]
         hb = ssm_b
         if ssm_b.dtype != ssm_f.dtype or ssm_b.stride() != ssm_f.stride():
             hb = torch.empty_strided(ssm_f.shape, ssm_f.stride(), dtype=ssm_f.dtype,
                                      device=dev).copy_(ssm_b)
         y = torch.empty_like(u)
-        s_u, s_xz, s_bc = (Lp * Dm, 1, Dm), (Lp * 2 * Dm, 1, 2 * Dm), (Lp * E, 1, E)
-        hs = (ssm_f.stride(0), ssm_f.stride(1))
+        s_u, s_xz, s_bc = mf._tm_strides(Lp)
+        hs = K.strides2(ssm_f)
         K.scan_raw(u, s_u, dt, s_u, A_f, x_dbl[:, R:R + N], s_bc, x_dbl[:, R + N:], s_bc, D_f,
                    xz[:, Dm:], s_xz, bias_f, True, ssm_f, hs, ssm_f, hs, y, s_u, Lp, 2 * B, Dm,
                    L, N, K.dtype_code(hdt), torch.cuda.current_stream(dev).cuda_stream,

@@ -68,7 +68,7 @@
 extern "C" {
 #endif
 
-#define VM_ABI_VERSION 18
+#define VM_ABI_VERSION 19 /* entries added after v18 are declared in videomamba_hip_ext.h */
 
 #define VM_DTYPE_F32 0
 #define VM_DTYPE_BF16 1

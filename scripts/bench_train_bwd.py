@@ -18,11 +18,17 @@ each leg once with ``options.train_gemm = "hip"`` (in_proj / out_proj through
   out_proj  the same for 1152 -> 576
   block, model  as above
 ``--compare ops`` is the comparison described first (conv, norm, block, model).
+``--compare refiner`` (ABI v19) times one training ``BiMambaRefinerBlock`` (C = 576, a
+(B, 8, 196, 576) input, B = 1, 2, 4, 8 by default) once with ``options.train_refiner = "paired"``
+(one vm_selective_scan_bidir_bwd launch over the 2 B rows of both directions) and once with
+``"blocks"`` (the composition on the differentiable ``Block``: two vm_selective_scan_bwd launches
+of B rows); ``verdict`` then carries, per batch, both medians and the larger min-to-max spread.
 Every measurement runs in a child process of its own under a time limit, so a slow leg cannot
 hold the device for minutes.  ``verdict`` says, per leg and batch, whether the HIP median is
 within the other side's median plus the larger min-to-max spread of the two.
 
     python scripts/bench_train_bwd.py [--batches 8 32] [--reps 20] > profiles/train_bwd_<tag>.json
+    python scripts/bench_train_bwd.py --compare refiner > profiles/train_refiner_<tag>.json
 """
 import argparse
 import json
@@ -34,7 +40,8 @@ import sys
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 DMODEL, DIM, SEQLEN, WIDTH, DEPTH, FRAMES = 576, 1152, 1569, 4, 32, 8
-LEGS = ("conv", "norm", "in_proj", "out_proj", "block", "model")
+LEGS = ("conv", "norm", "in_proj", "out_proj", "block", "model", "refiner")
+REFINER_TOKENS, REFINER_BATCHES = 196, (1, 2, 4, 8)  # (B, FRAMES, 196, DMODEL) inputs
 COMPARE = {"ops": (("conv", "norm", "block", "model"), "torch"),
            "gemm": (("in_proj", "out_proj", "block", "model"), "library")}
 PROJ = {"in_proj": (2 * DIM, DMODEL), "out_proj": (DMODEL, DIM)}  # (n, k)
@@ -164,15 +171,71 @@ def _model(batch, ops, gemm, dev):
     return pair
 
 
-def child(leg, batch, ops, gemm, warmup, reps):
+def _refiner(batch, mode, dev):
+    import torch
+    from videomamba_amd import options
+    from videomamba_amd.refiner_backbone import BiMambaRefinerBlock
+    torch.manual_seed(0)
+    blk = BiMambaRefinerBlock(DMODEL, layer_idx=0).to(torch.bfloat16).to(dev).train()
+    g = torch.Generator().manual_seed(batch)
+    shape = (batch, FRAMES, REFINER_TOKENS, DMODEL)
+    x = torch.randn(*shape, generator=g).to(torch.bfloat16).to(dev).requires_grad_(True)
+    gy = torch.randn(*shape, generator=g).to(torch.bfloat16).to(dev)
+    leaves = [x] + list(blk.parameters())
+
+    def pair():
+        with options.override(train_refiner=mode):
+            out, _ = blk(x)
+            torch.autograd.grad(out, leaves, gy)
+
+    return pair
+
+
+def child(leg, batch, ops, gemm, warmup, reps, refiner="paired"):
     import torch
     assert torch.cuda.is_available(), "this benchmark needs the GPU"
     dev = torch.device("cuda", 0)
+    if leg == "refiner":
+        t = _time(_refiner(batch, refiner, dev), warmup, reps)
+        return dict(leg=leg, batch=batch, refiner=refiner, fwd_bwd_us=t,
+                    peak_mem_mb=round(torch.cuda.max_memory_allocated() / 2 ** 20))
     fn = {"conv": _conv, "norm": _norm, "in_proj": _proj("in_proj"), "out_proj": _proj("out_proj"),
           "block": _block, "model": _model}[leg](batch, ops, gemm, dev)
     t = _time(fn, warmup, reps)
     return dict(leg=leg, batch=batch, ops=ops, gemm=gemm, fwd_bwd_us=t,
                 peak_mem_mb=round(torch.cuda.max_memory_allocated() / 2 ** 20))
+
+
+def _main_refiner(a):
+    """``--compare refiner``: "paired" against "blocks" per batch, a child process each."""
+    out = dict(bench="train_bwd", compare="refiner", d_model=DMODEL, d_inner=DIM,
+               seqlen=FRAMES * REFINER_TOKENS, frames=FRAMES, dtype="bf16", reps=a.reps,
+               warmup=a.warmup, timer="device events", results=[], verdict=[])
+    for b in a.batches or REFINER_BATCHES:
+        pair = {}
+        for mode in ("paired", "blocks"):
+            cmd = ["timeout", "-k", "10", str(a.limit), sys.executable, os.path.abspath(__file__),
+                   "--child", "refiner", "--batch", str(b), "--refiner", mode,
+                   "--reps", str(a.reps), "--warmup", str(a.warmup)]
+            run = subprocess.run(cmd, capture_output=True, text=True)
+            if run.returncode != 0:  # a faulted or hung leg: start nothing more on the device
+                out["results"].append(dict(leg="refiner", batch=b, refiner=mode,
+                                           error=f"exit {run.returncode}",
+                                           stderr=run.stderr[-400:]))
+                print(json.dumps(out), flush=True)
+                return 1
+            r = json.loads(run.stdout.strip().splitlines()[-1])
+            out["results"].append(r)
+            pair[mode] = r["fwd_bwd_us"]
+        spread = max(p["max"] - p["min"] for p in pair.values())
+        pm, bm = pair["paired"]["median"], pair["blocks"]["median"]
+        out["verdict"].append({
+            "leg": "refiner", "batch": b, "paired_us": pm, "blocks_us": bm,
+            "spread_us": round(spread, 1), "blocks_over_paired": round(bm / pm, 2),
+            "paired_faster_beyond_spread": pm < bm - spread,
+            "paired_not_slower": pm <= bm + spread})
+    print(json.dumps(out), flush=True)
+    return 0
 
 
 def _run_child(leg, batch, ops, gemm, a):
@@ -188,8 +251,9 @@ def _run_child(leg, batch, ops, gemm, a):
 
 def main():
     ap = argparse.ArgumentParser()
-    ap.add_argument("--batches", type=int, nargs="+", default=[8, 32])
-    ap.add_argument("--compare", choices=list(COMPARE), default="gemm")
+    ap.add_argument("--batches", type=int, nargs="+", default=None,
+                    help="default 8 32 (--compare refiner: 1 2 4 8)")
+    ap.add_argument("--compare", choices=list(COMPARE) + ["refiner"], default="gemm")
     ap.add_argument("--legs", nargs="+", choices=LEGS, default=None)
     ap.add_argument("--reps", type=int, default=20)
     ap.add_argument("--warmup", type=int, default=3)
@@ -198,12 +262,17 @@ def main():
     ap.add_argument("--batch", type=int, default=8)
     ap.add_argument("--ops", choices=["hip", "torch"], default="hip")
     ap.add_argument("--gemm", choices=["hip", "library"], default="library")
+    ap.add_argument("--refiner", choices=["paired", "blocks"], default="paired")
     a = ap.parse_args()
     if a.reps < 20:
         ap.error("--reps must be at least 20")
     if a.child:
-        print(json.dumps(child(a.child, a.batch, a.ops, a.gemm, a.warmup, a.reps)), flush=True)
+        print(json.dumps(child(a.child, a.batch, a.ops, a.gemm, a.warmup, a.reps, a.refiner)),
+              flush=True)
         return 0
+    if a.compare == "refiner":
+        return _main_refiner(a)
+    a.batches = a.batches or [8, 32]
     legs, other = COMPARE[a.compare]
     legs = [leg for leg in (a.legs or legs) if leg in legs]
     out = dict(bench="train_bwd", compare=a.compare, d_model=DMODEL, d_inner=DIM, seqlen=SEQLEN, depth=DEPTH,

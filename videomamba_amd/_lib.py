@@ -1,4 +1,5 @@
-"""ctypes binding of ``libvideomamba_hip.so`` (the C ABI in ``include/videomamba_hip.h``).
+"""ctypes binding of ``libvideomamba_hip.so`` (the C ABI in ``include/videomamba_hip.h`` and,
+for entries added after ABI v18, ``include/videomamba_hip_ext.h``).
 
 The library is built in-tree (``make -C videomamba_amd/csrc`` or
 ``__graft_entry__.build()``).  There is no fallback: if the library is missing or fails
@@ -20,7 +21,7 @@ LIB_PATH = os.path.join(os.path.dirname(os.path.abspath(__file__)), LIB_NAME)
 
 VM_DTYPE_F32 = 0
 VM_DTYPE_BF16 = 1
-ABI_VERSION = 18
+ABI_VERSION = 19
 
 _P = c_void_p
 _LL = c_longlong
@@ -187,6 +188,17 @@ _SIGNATURES = {
 
 EXPORTED = tuple(_SIGNATURES)
 
+# Entries added after ABI v18, declared in ``include/videomamba_hip_ext.h``.
+_SIGNATURES_EXT = {
+    "vm_selective_scan_bidir_bwd": (
+        _SIGNATURES["vm_selective_scan_bwd"][0][:-3] +  # vm_selective_scan_bwd's, up to dtype
+        [_I, _P, _P, _P, _P, _P,   # split, A / D / delta_bias / h0 / dh_last bwd
+         _P, _P, _P, _P, _I,       # dA / dD / ddelta_bias / dh0 bwd, frame_len
+         _P, _LL, _P], _I),        # workspace, bytes, stream
+}
+
+EXPORTED_EXT = tuple(_SIGNATURES_EXT)
+
 _lib = None
 _load_error: str | None = None
 
@@ -207,7 +219,7 @@ def load():
     except OSError as exc:
         _load_error = f"failed to load {LIB_PATH}: {exc}"
         raise RuntimeError(_load_error) from exc
-    for name, (args, res) in _SIGNATURES.items():
+    for name, (args, res) in {**_SIGNATURES, **_SIGNATURES_EXT}.items():
         fn = getattr(lib, name)
         fn.argtypes = args
         fn.restype = res

@@ -48,6 +48,20 @@ __device__ __forceinline__ PairSel pair_sel(const ScanParams& p, int b) {
   return {p.A, p.D, p.dbias, p.h0, p.hl, b, 0, 1, 0, 0u};
 }
 
+// The constants of PairSel::orow for the backward direction of a paired scan over `seqlen`
+// steps in frames of F (F >= 1 divides seqlen, seqlen * F < 2^31): step t's output row is
+// t + (L - F) - 2F floor(t / F) — reversed frame order, the steps within a frame in order;
+// floor by a reciprocal multiply, exact for L*F < 2^32.  The forward entry stores through
+// it and the backward entry (vm_scan_bwd.hip) reads dout through it.
+inline void pair_row_map(int seqlen, int F, int& c0, int& s, int& c1, unsigned& m) {
+  if (F == 1) {
+    c0 = seqlen - 1; s = -1; c1 = 0; m = 0u;
+  } else {
+    c0 = seqlen - F; s = 1; c1 = 2 * F;
+    m = static_cast<unsigned>(0xffffffffu / static_cast<unsigned>(F)) + 1u;
+  }
+}
+
 
 // Token-major path (vm_scan_seq.hip).  Every decision about its form, geometry and buffer
 // layout is a ScanPlan (vm_scan_plan.h).

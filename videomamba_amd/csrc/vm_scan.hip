@@ -542,14 +542,7 @@ static int scan_entry(const char* name, VM_SCAN_ARGS, const PairArgs* pair, int 
     }
     p.split = pair->split; p.A_hi = pair->A; p.D_hi = pair->D; p.dbias_hi = pair->dbias;
     p.h0_hi = pair->h0; p.hl_hi = pair->hl;
-    // output row of step t: t + (L - F) - 2F floor(t / F) (reversed frame order, tokens
-    // within a frame in order); floor by a reciprocal multiply, exact for L*F < 2^32
-    if (F == 1) {
-      p.ro_c0 = seqlen - 1; p.ro_s = -1; p.ro_c1 = 0; p.ro_m = 0u;
-    } else {
-      p.ro_c0 = seqlen - F; p.ro_s = 1; p.ro_c1 = 2 * F;
-      p.ro_m = static_cast<unsigned>(0xffffffffu / static_cast<unsigned>(F)) + 1u;
-    }
+    pair_row_map(seqlen, F, p.ro_c0, p.ro_s, p.ro_c1, p.ro_m);
   }
   // Token-major operands (channel stride 1): channel-per-lane sequential kernels.
   if (token_major) {

@@ -30,7 +30,18 @@
 // Lanes at or past dim and steps at or past seqlen load nothing outside the operands (they
 // re-read the last channel / step and use 0 instead, so they add 0 to every sum) and store
 // nothing outside the workspace's padded rows.
+//
+// Paired form (vm_selective_scan_bidir_bwd, PAIR): the gradient of vm_selective_scan_bidir_fwd
+// over batch = 2 split rows in one launch.  A workgroup of a row b >= split (uniform per
+// workgroup, so the choice is scalar) takes the backward direction's A / D / bias, its states
+// at row b - split, and reads step t's dout at the un-flipped row the forward stored step t's
+// output at (PairSel::orow, vm_scan.h); every other operand and gradient stays in flipped
+// step order.  The reduce adds the dA / dD / dbias partials of rows [0, split) into the
+// forward direction's outputs and those of [split, 2 split) into the backward direction's,
+// each in batch-row order: either half's bits are those of a plain launch over its rows.
 #include "vm_common.h"
+#include "../../include/videomamba_hip_ext.h"
+#include "vm_scan.h"
 #include "vm_scan_bwd_plan.h"
 
 namespace vm {
@@ -47,6 +58,32 @@ struct ScanBwdParams {
   long long dB_sb, dB_sn, dB_sl, dC_sb, dC_sn, dC_sl, dh0_sb, dh0_sd;
   int batch, dim, seqlen, softplus, h0_dtype;
 };
+
+// The backward direction of a paired launch: the parameter set, states and parameter
+// gradients of batch rows b >= split (state row b - split, the forward direction's dtypes and
+// strides) and the constants of their dout row map.  A trailing kernel argument of its own,
+// so the plain kernels' argument layout stays what it was.
+struct ScanBwdPair {
+  int split;
+  const float* A; const float* D; const float* dbias; const void* h0; const float* dhl;
+  float* dA; float* dD; float* ddbias; float* dh0;
+  int ro_c0, ro_s, ro_c1; unsigned ro_m;
+};
+
+// Parameter set of batch row b (uniform per workgroup): PairSel's parameters, entry state and
+// row map (its last-state slot is unused here) and the state gradients.  PAIR = false folds to
+// the plain launch's at compile time.
+struct BwdSel {
+  PairSel s;
+  const float* dhl; float* dh0;
+};
+template <bool PAIR>
+__device__ __forceinline__ BwdSel bwd_sel(const ScanBwdParams& p, const ScanBwdPair& q, int b) {
+  if (PAIR && b >= q.split)
+    return {{q.A, q.D, q.dbias, q.h0, nullptr, b - q.split, q.ro_c0, q.ro_s, q.ro_c1, q.ro_m},
+            q.dhl, q.dh0};
+  return {{p.A, p.D, p.dbias, p.h0, nullptr, b, 0, 1, 0, 0u}, p.dhl, p.dh0};
+}
 
 __device__ __forceinline__ float lane_value(float v, int l) {
   return __int_as_float(__builtin_amdgcn_readlane(__float_as_int(v), l));
@@ -83,10 +120,11 @@ __device__ __forceinline__ int bitrev3(int l) {
   return ((l & 1) << 2) | (l & 2) | ((l & 4) >> 2);
 }
 
-template <typename T, bool HAS_Z>
+template <typename T, bool HAS_Z, bool PAIR>
 __global__ __launch_bounds__(kBwdLanes * kBwdWaves) void scan_bwd_kernel(const ScanBwdParams p,
                                                                          const ScanBwdPlan pl,
-                                                                         float* ws) {
+                                                                         float* ws,
+                                                                         const ScanBwdPair q) {
   constexpr int NS = kBwdNS;  // states per wave
   // the state entering each step of a chunk, [wave][step][state][lane]
   __shared__ float hs_all[kBwdWaves * kBwdT * NS * kBwdLanes];
@@ -101,15 +139,18 @@ __global__ __launch_bounds__(kBwdLanes * kBwdWaves) void scan_bwd_kernel(const S
   const bool live = d < p.dim;
   const int L = p.seqlen;
   const int nch = pl.nchunks;
+  const BwdSel sel = bwd_sel<PAIR>(p, q, b);
+  const PairSel& ps = sel.s;
+  const int hb = PAIR ? ps.hb : b;  // the state row of this batch row
 
   float A1[NS], A2[NS];  // A and A log2(e)
 #pragma unroll
   for (int n = 0; n < NS; ++n) {
-    A1[n] = live ? p.A[static_cast<long long>(d) * kBwdN + n0 + n] : 0.0f;
+    A1[n] = live ? ps.A[static_cast<long long>(d) * kBwdN + n0 + n] : 0.0f;
     A2[n] = A1[n] * kLog2e;
   }
-  const float Dv = (p.D && live) ? p.D[d] : 0.0f;
-  const float bias = (p.dbias && live) ? p.dbias[d] : 0.0f;
+  const float Dv = (ps.D && live) ? ps.D[d] : 0.0f;
+  const float bias = (ps.dbias && live) ? ps.dbias[d] : 0.0f;
   // Every operand load is unconditional from an address inside the operand: a lane past dim
   // reads channel dim - 1, a step past seqlen reads step seqlen - 1, and the value is then
   // replaced by 0.  (A load under a lane-dependent branch is waited for on the spot, which
@@ -129,8 +170,8 @@ __global__ __launch_bounds__(kBwdLanes * kBwdWaves) void scan_bwd_kernel(const S
   auto entry_state = [&](float (&h)[NS]) {
 #pragma unroll
     for (int n = 0; n < NS; ++n)
-      h[n] = (p.h0 && live) ? load_dyn(p.h0, b * p.h0_sb + d * p.h0_sd + n0 + n, p.h0_dtype)
-                            : 0.0f;
+      h[n] = (ps.h0 && live) ? load_dyn(ps.h0, hb * p.h0_sb + d * p.h0_sd + n0 + n, p.h0_dtype)
+                             : 0.0f;
   };
   auto step_size = [&](float raw) { return p.softplus ? softplus_fast(raw) : raw; };
   auto ckpt_at = [&](int c) {  // this wave's states entering chunk c >= 1
@@ -175,7 +216,7 @@ __global__ __launch_bounds__(kBwdLanes * kBwdWaves) void scan_bwd_kernel(const S
   float accD = 0.0f, accB = 0.0f;  // wave 0 only
 #pragma unroll
   for (int n = 0; n < NS; ++n) {
-    gc[n] = (p.dhl && live) ? p.dhl[b * p.dhl_sb + d * p.dhl_sd + n0 + n] : 0.0f;
+    gc[n] = (sel.dhl && live) ? sel.dhl[hb * p.dhl_sb + d * p.dhl_sd + n0 + n] : 0.0f;
     accA[n] = 0.0f;
   }
   T* dup = static_cast<T*>(p.du) + b * p.du_sb + d;
@@ -203,7 +244,9 @@ __global__ __launch_bounds__(kBwdLanes * kBwdWaves) void scan_bwd_kernel(const S
       const long long t = s < nst ? t0 + s : L - 1;
       const bool on = s < nst && live;
       const float uv = to_f32(up[t * p.u_sl]), dv = to_f32(dlp[t * p.dl_sl]);
-      const float gv = to_f32(gop[t * p.do_sl]);
+      // paired: the row the forward stored step t's output at (the clamped step's: a valid row)
+      const long long tg = PAIR ? ps.orow(static_cast<int>(t)) : t;
+      const float gv = to_f32(gop[tg * p.do_sl]);
       uu[s] = on ? uv : 0.0f;
       raw[s] = on ? dv + bias : 0.0f;
       go[s] = on ? gv : 0.0f;
@@ -312,9 +355,9 @@ __global__ __launch_bounds__(kBwdLanes * kBwdWaves) void scan_bwd_kernel(const S
     __syncthreads();  // xch is free for the next chunk
   }
 
-  if (p.dh0 && live) {
+  if (sel.dh0 && live) {
 #pragma unroll
-    for (int n = 0; n < NS; ++n) p.dh0[b * p.dh0_sb + d * p.dh0_sd + n0 + n] = gc[n];
+    for (int n = 0; n < NS; ++n) sel.dh0[hb * p.dh0_sb + d * p.dh0_sd + n0 + n] = gc[n];
   }
   const size_t row = static_cast<size_t>(b) * pl.dpad + d;  // d < dpad: inside the padded rows
 #pragma unroll
@@ -327,10 +370,13 @@ __global__ __launch_bounds__(kBwdLanes * kBwdWaves) void scan_bwd_kernel(const S
 
 // dB | dC: the group partials of every (batch row, step, state) added in group order; dA, dD,
 // dbias: the batch-row partials added in batch order.  One thread per output element.
-template <typename T>
+// PAIR: two sets of dA / dD / dbias, the forward direction's from rows [0, split) and the
+// backward direction's from rows [split, batch), each from 0 in batch order.
+template <typename T, bool PAIR>
 __global__ __launch_bounds__(256) void scan_bwd_reduce_kernel(const ScanBwdParams p,
                                                               const ScanBwdPlan pl,
-                                                              const float* ws) {
+                                                              const float* ws,
+                                                              const ScanBwdPair q) {
   const long long i = static_cast<long long>(blockIdx.x) * 256 + threadIdx.x;
   const long long L = p.seqlen;
   const long long nbc = static_cast<long long>(p.batch) * L * (2 * kBwdN);
@@ -347,43 +393,56 @@ __global__ __launch_bounds__(256) void scan_bwd_reduce_kernel(const ScanBwdParam
       static_cast<T*>(p.dC)[b * p.dC_sb + (j - kBwdN) * p.dC_sn + t * p.dC_sl] = from_f32<T>(acc);
     return;
   }
-  const long long k = i - nbc;
+  long long k = i - nbc;
   const long long na = static_cast<long long>(p.dim) * kBwdN;
+  int b0 = 0, b1 = p.batch;  // the batch rows summed
+  float* dA = p.dA;
+  float* dD = p.dD;
+  float* ddbias = p.ddbias;
+  if (PAIR) {
+    b1 = q.split;
+    if (k >= na + p.dim) {  // the backward direction's set
+      k -= na + p.dim;
+      b0 = q.split; b1 = p.batch;
+      dA = q.dA; dD = q.dD; ddbias = q.ddbias;
+    }
+  }
   if (k < na) {
     const long long d = k / kBwdN;
     const int n = static_cast<int>(k % kBwdN);
     float acc = 0.0f;
-    for (int b = 0; b < p.batch; ++b)
+    for (int b = b0; b < b1; ++b)
       acc += ws[pl.pa + (static_cast<size_t>(b) * pl.dpad + d) * kBwdN + n];
-    p.dA[k] = acc;
+    dA[k] = acc;
   } else if (k < na + p.dim) {
     const long long d = k - na;
     float accD = 0.0f, accB = 0.0f;
-    for (int b = 0; b < p.batch; ++b) {
+    for (int b = b0; b < b1; ++b) {
       accD += ws[pl.pd + static_cast<size_t>(b) * pl.dpad + d];
       accB += ws[pl.pb + static_cast<size_t>(b) * pl.dpad + d];
     }
-    if (p.dD) p.dD[d] = accD;
-    if (p.ddbias) p.ddbias[d] = accB;
+    if (dD) dD[d] = accD;
+    if (ddbias) ddbias[d] = accB;
   }
 }
 
-template <typename T>
-static void scan_bwd_launch(const ScanBwdParams& p, const ScanBwdPlan& pl, float* ws,
-                            hipStream_t s) {
+template <typename T, bool PAIR>
+static void scan_bwd_launch(const ScanBwdParams& p, const ScanBwdPair& q, const ScanBwdPlan& pl,
+                            float* ws, hipStream_t s) {
   if (p.batch > 0) {
     const dim3 grid(pl.groups, p.batch);
     if (p.z)
-      hipLaunchKernelGGL((scan_bwd_kernel<T, true>), grid, dim3(kBwdLanes * kBwdWaves), 0, s, p,
-                         pl, ws);
+      hipLaunchKernelGGL((scan_bwd_kernel<T, true, PAIR>), grid, dim3(kBwdLanes * kBwdWaves), 0,
+                         s, p, pl, ws, q);
     else
-      hipLaunchKernelGGL((scan_bwd_kernel<T, false>), grid, dim3(kBwdLanes * kBwdWaves), 0, s, p,
-                         pl, ws);
+      hipLaunchKernelGGL((scan_bwd_kernel<T, false, PAIR>), grid, dim3(kBwdLanes * kBwdWaves), 0,
+                         s, p, pl, ws, q);
   }
   const long long outs = static_cast<long long>(p.batch) * p.seqlen * (2 * kBwdN) +
-                         static_cast<long long>(p.dim) * (kBwdN + 1);
-  hipLaunchKernelGGL((scan_bwd_reduce_kernel<T>), dim3(static_cast<unsigned>((outs + 255) / 256)),
-                     dim3(256), 0, s, p, pl, ws);
+                         static_cast<long long>(p.dim) * (kBwdN + 1) * (PAIR ? 2 : 1);
+  hipLaunchKernelGGL((scan_bwd_reduce_kernel<T, PAIR>),
+                     dim3(static_cast<unsigned>((outs + 255) / 256)), dim3(256), 0, s, p, pl, ws,
+                     q);
 }
 
 }  // namespace vm
@@ -396,25 +455,39 @@ extern "C" long long vm_selective_scan_bwd_workspace_bytes(int batch, int dim, i
   return static_cast<long long>(plan_scan_bwd(batch, dim, seqlen).ws_bytes);
 }
 
-extern "C" int vm_selective_scan_bwd(
-    const void* u, long long u_sb, long long u_sd, long long u_sl,
-    const void* delta, long long dl_sb, long long dl_sd, long long dl_sl, const float* A,
-    const void* B, long long b_sb, long long b_sn, long long b_sl,
-    const void* C, long long c_sb, long long c_sn, long long c_sl,
-    const float* D, const void* z, long long z_sb, long long z_sd, long long z_sl,
-    const float* delta_bias, int delta_softplus,
-    const void* h0, int h0_dtype, long long h0_sb, long long h0_sd,
-    const void* dout, long long do_sb, long long do_sd, long long do_sl,
-    const float* dh_last, long long dhl_sb, long long dhl_sd,
-    void* du, long long du_sb, long long du_sd, long long du_sl,
-    void* ddelta, long long dd_sb, long long dd_sd, long long dd_sl,
-    void* dz, long long dz_sb, long long dz_sd, long long dz_sl,
-    void* dB, long long dB_sb, long long dB_sn, long long dB_sl,
-    void* dC, long long dC_sb, long long dC_sn, long long dC_sl,
-    float* dA, float* dD, float* ddelta_bias, float* dh0, long long dh0_sb, long long dh0_sd,
-    int batch, int dim, int seqlen, int dstate, int dtype,
-    void* workspace, long long workspace_bytes, vm_stream_t stream) {
-  const char* name = "vm_selective_scan_bwd";
+namespace {
+// The backward direction's arguments of the paired entry; nullptr for the plain entry.
+struct PairBwdArgs {
+  int split; const float* A; const float* D; const float* dbias; const void* h0;
+  const float* dhl; float* dA; float* dD; float* ddbias; float* dh0; int frame_len;
+};
+}  // namespace
+
+#define VM_SCAN_BWD_ARGS                                                                        \
+  const void *u, long long u_sb, long long u_sd, long long u_sl, const void *delta,             \
+      long long dl_sb, long long dl_sd, long long dl_sl, const float *A, const void *B,         \
+      long long b_sb, long long b_sn, long long b_sl, const void *C, long long c_sb,            \
+      long long c_sn, long long c_sl, const float *D, const void *z, long long z_sb,            \
+      long long z_sd, long long z_sl, const float *delta_bias, int delta_softplus,              \
+      const void *h0, int h0_dtype, long long h0_sb, long long h0_sd, const void *dout,         \
+      long long do_sb, long long do_sd, long long do_sl, const float *dh_last,                  \
+      long long dhl_sb, long long dhl_sd, void *du, long long du_sb, long long du_sd,           \
+      long long du_sl, void *ddelta, long long dd_sb, long long dd_sd, long long dd_sl,         \
+      void *dz, long long dz_sb, long long dz_sd, long long dz_sl, void *dB, long long dB_sb,   \
+      long long dB_sn, long long dB_sl, void *dC, long long dC_sb, long long dC_sn,             \
+      long long dC_sl, float *dA, float *dD, float *ddelta_bias, float *dh0, long long dh0_sb,  \
+      long long dh0_sd, int batch, int dim, int seqlen, int dstate, int dtype
+#define VM_SCAN_BWD_PASS                                                                        \
+  u, u_sb, u_sd, u_sl, delta, dl_sb, dl_sd, dl_sl, A, B, b_sb, b_sn, b_sl, C, c_sb, c_sn, c_sl, \
+      D, z, z_sb, z_sd, z_sl, delta_bias, delta_softplus, h0, h0_dtype, h0_sb, h0_sd, dout,     \
+      do_sb, do_sd, do_sl, dh_last, dhl_sb, dhl_sd, du, du_sb, du_sd, du_sl, ddelta, dd_sb,     \
+      dd_sd, dd_sl, dz, dz_sb, dz_sd, dz_sl, dB, dB_sb, dB_sn, dB_sl, dC, dC_sb, dC_sn, dC_sl,  \
+      dA, dD, ddelta_bias, dh0, dh0_sb, dh0_sd, batch, dim, seqlen, dstate, dtype
+
+// Both entries: every check, then the launch.  `pair` adds the paired entry's checks and
+// selects the PAIR kernels.
+static int scan_bwd_entry(const char* name, VM_SCAN_BWD_ARGS, const PairBwdArgs* pair,
+                          void* workspace, long long workspace_bytes, vm_stream_t stream) {
   if (!u || !delta || !A || !B || !C || !dout || !du || !ddelta || !dB || !dC || !dA ||
       (z != nullptr) != (dz != nullptr) || (D != nullptr) != (dD != nullptr) ||
       (delta_bias != nullptr) != (ddelta_bias != nullptr)) {
@@ -422,10 +495,35 @@ extern "C" int vm_selective_scan_bwd(
                       "delta_bias)", name);
     return VM_E_INVALID;
   }
+  if (pair && (!pair->A || !pair->dA || (pair->D != nullptr) != (pair->dD != nullptr) ||
+               (pair->dbias != nullptr) != (pair->ddbias != nullptr))) {
+    vmhost::set_error("%s: null required pointer (A_bwd and dA_bwd are required; dD_bwd / "
+                      "ddelta_bias_bwd go with D_bwd / delta_bias_bwd)", name);
+    return VM_E_INVALID;
+  }
   if (batch < 0 || dim < 0 || seqlen < 0 || dstate != kBwdN) {
     vmhost::set_error("%s: bad shape batch=%d dim=%d seqlen=%d dstate=%d (dstate must be %d)",
                       name, batch, dim, seqlen, dstate, kBwdN);
     return VM_E_INVALID;
+  }
+  if (pair) {
+    const int F = pair->frame_len;
+    if (pair->split < 0 || 2ll * pair->split != batch) {
+      vmhost::set_error("%s: batch=%d must be 2*split (split=%d)", name, batch, pair->split);
+      return VM_E_INVALID;
+    }
+    if (F < 1 || seqlen % F || static_cast<long long>(seqlen) * F >= (1ll << 31)) {
+      vmhost::set_error("%s: frame_len=%d must be >= 1 and divide seqlen=%d "
+                        "(seqlen * frame_len < 2^31)", name, F, seqlen);
+      return VM_E_INVALID;
+    }
+    if ((D != nullptr) != (pair->D != nullptr) ||
+        (delta_bias != nullptr) != (pair->dbias != nullptr) ||
+        (h0 != nullptr) != (pair->h0 != nullptr)) {
+      vmhost::set_error("%s: D / delta_bias / h0 must be present in both directions or in "
+                        "neither", name);
+      return VM_E_INVALID;
+    }
   }
   if (!vmhost::dtype_ok(dtype) || (h0 && !vmhost::dtype_ok(h0_dtype))) {
     vmhost::set_error("%s: unsupported dtype", name);
@@ -461,7 +559,37 @@ extern "C" int vm_selective_scan_bwd(
   p.batch = batch; p.dim = dim; p.seqlen = seqlen; p.softplus = delta_softplus;
   p.h0_dtype = h0_dtype;
   hipStream_t s = static_cast<hipStream_t>(stream);
-  if (dtype == VM_DTYPE_BF16) scan_bwd_launch<bf16_t>(p, pl, static_cast<float*>(workspace), s);
-  else scan_bwd_launch<float>(p, pl, static_cast<float*>(workspace), s);
+  float* ws = static_cast<float*>(workspace);
+  ScanBwdPair q{};
+  if (pair) {
+    q.split = pair->split; q.A = pair->A; q.D = pair->D; q.dbias = pair->dbias; q.h0 = pair->h0;
+    q.dhl = pair->dhl; q.dA = pair->dA; q.dD = pair->dD; q.ddbias = pair->ddbias;
+    q.dh0 = pair->dh0;
+    pair_row_map(seqlen, pair->frame_len, q.ro_c0, q.ro_s, q.ro_c1, q.ro_m);
+    if (dtype == VM_DTYPE_BF16) scan_bwd_launch<bf16_t, true>(p, q, pl, ws, s);
+    else scan_bwd_launch<float, true>(p, q, pl, ws, s);
+  } else {
+    if (dtype == VM_DTYPE_BF16) scan_bwd_launch<bf16_t, false>(p, q, pl, ws, s);
+    else scan_bwd_launch<float, false>(p, q, pl, ws, s);
+  }
   return vmhost::launch_status(name);
 }
+
+extern "C" int vm_selective_scan_bwd(VM_SCAN_BWD_ARGS, void* workspace,
+                                     long long workspace_bytes, vm_stream_t stream) {
+  return scan_bwd_entry("vm_selective_scan_bwd", VM_SCAN_BWD_PASS, nullptr, workspace,
+                        workspace_bytes, stream);
+}
+
+extern "C" int vm_selective_scan_bidir_bwd(VM_SCAN_BWD_ARGS, int split, const float* A_bwd,
+                                           const float* D_bwd, const float* delta_bias_bwd,
+                                           const void* h0_bwd, const float* dh_last_bwd,
+                                           float* dA_bwd, float* dD_bwd, float* ddelta_bias_bwd,
+                                           float* dh0_bwd, int frame_len, void* workspace,
+                                           long long workspace_bytes, vm_stream_t stream) {
+  const PairBwdArgs pair{split, A_bwd, D_bwd, delta_bias_bwd, h0_bwd, dh_last_bwd,
+                         dA_bwd, dD_bwd, ddelta_bias_bwd, dh0_bwd, frame_len};
+  return scan_bwd_entry("vm_selective_scan_bidir_bwd", VM_SCAN_BWD_PASS, &pair, workspace,
+                        workspace_bytes, stream);
+}
+

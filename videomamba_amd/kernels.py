@@ -6,6 +6,9 @@ Public functions keep the call shapes the reference uses for its third-party ker
 * ``selective_scan_fn``      <- mamba_ssm ``selective_scan_fn`` (+ ``initial_state``),
   differentiable: with grad mode on and an operand that requires grad it builds an autograd
   graph whose backward is the HIP kernel ``vm_selective_scan_bwd``
+* ``selective_scan_bidir_fn`` <- the refiner's two ``selective_scan_fn`` calls (forward and
+  flipped) as one paired scan, differentiable the same way (``vm_selective_scan_bidir_fwd`` /
+  ``vm_selective_scan_bidir_bwd``)
 * ``selective_state_update`` <- mamba_ssm Triton ``selective_state_update``
 * ``causal_conv1d_fn`` / ``causal_conv1d_update`` <- causal-conv1d; ``causal_conv1d_fn`` is
   differentiable the same way (``vm_causal_conv1d_bwd``, width <= 4)
@@ -361,6 +364,37 @@ def selective_scan_bwd_raw(u, u_s, delta, dl_s, A32, B, b_s, C, c_s, D32, z, z_s
         _p(dA), _p(dD), _p(dbias), _p(dh0), *dh0_s[:2],
         batch, dim, seqlen, dstate, dtype, _p(ws), ws_bytes, stream)
     _lib.check(rc, "vm_selective_scan_bwd")
+
+
+def selective_scan_bidir_bwd_raw(u, u_s, delta, dl_s, A32, B, b_s, C, c_s, D32, z, z_s, bias32,
+                                 softplus, h0, h0_s, dout, do_s, dh_last, dhl_s, du, du_s,
+                                 ddelta, dd_s, dz, dz_s, dB, dB_s, dC, dC_s, dA, dD, dbias, dh0,
+                                 dh0_s, batch, dim, seqlen, dstate, dtype, stream, pair,
+                                 workspace: Optional[Tensor] = None):
+    """``vm_selective_scan_bidir_bwd``: the gradients of :func:`scan_raw` with ``pair=`` over
+    ``batch = 2 split`` token-major rows in one launch.  The arguments up to ``stream`` are
+    :func:`selective_scan_bwd_raw`'s and name the forward direction's parameters, states and
+    parameter gradients (states of ``split`` rows); ``pair`` = (split, A32_bwd, D32_bwd,
+    bias32_bwd, h0_bwd, dh_last_bwd, dA_bwd, dD_bwd, dbias_bwd, dh0_bwd, frame_len) the backward
+    direction's, its states with the forward direction's dtypes and strides.  ``dout`` is the
+    gradient of the paired forward's output (backward rows un-flipped); du / ddelta / dz / dB /
+    dC of the backward rows come back in flipped step order, as their operands lie.  The
+    workspace is :func:`scan_bwd_workspace_bytes` of ``batch`` rows."""
+    lib = _lib.load()
+    ws_bytes = scan_bwd_workspace_bytes(batch, dim, seqlen, dstate)
+    ws = _workspace(u.device, stream, ws_bytes, workspace, "paired scan backward")
+    split, a_b, d_b, bias_b, h0_b, dhl_b, dA_b, dD_b, dbias_b, dh0_b, frame = pair
+    rc = lib.vm_selective_scan_bidir_bwd(
+        _p(u), *u_s, _p(delta), *dl_s, _p(A32), _p(B), *b_s, _p(C), *c_s,
+        _p(D32), _p(z), *z_s, _p(bias32), int(softplus),
+        _p(h0), dtype_code_of(h0), *h0_s[:2],
+        _p(dout), *do_s, _p(dh_last), *dhl_s[:2],
+        _p(du), *du_s, _p(ddelta), *dd_s, _p(dz), *dz_s, _p(dB), *dB_s, _p(dC), *dC_s,
+        _p(dA), _p(dD), _p(dbias), _p(dh0), *dh0_s[:2],
+        batch, dim, seqlen, dstate, dtype,
+        int(split), _p(a_b), _p(d_b), _p(bias_b), _p(h0_b), _p(dhl_b),
+        _p(dA_b), _p(dD_b), _p(dbias_b), _p(dh0_b), int(frame), _p(ws), ws_bytes, stream)
+    _lib.check(rc, "vm_selective_scan_bidir_bwd")
 
 
 def scan_chunk_steps(batch: int, dim: int, seqlen: int, dstate: int, segments: int = -1) -> int:
@@ -990,6 +1024,148 @@ def selective_scan_fn(u: Tensor, delta: Tensor, A: Tensor, B: Tensor, C: Tensor,
              f32c(delta_bias), delta_softplus, h0, strides2(h0), hl, strides2(hl),
              out, s3(out), seqlen, batch, dim, seqlen, dstate, dt, _stream(u))
     return (out, hl) if return_last_state else out
+
+
+def _scan_bidir_forward(u, delta, A, B, C, D, z, bias, A_b, D_b, bias_b, h0, h0_b, split,
+                        frame_len, softplus):
+    """The paired forward (:func:`scan_raw` with ``pair=``) on prepared operands: token-major
+    u / delta / z / B / C in u's dtype, fp32 contiguous parameters and entry states.  Returns
+    the output (backward rows un-flipped) and two new fp32 last states."""
+    batch, dim, seqlen = u.shape
+    n = A.shape[1]
+    out = torch.empty((batch, seqlen, dim), dtype=u.dtype, device=u.device).transpose(1, 2)
+    hl = torch.empty((split, dim, n), dtype=torch.float32, device=u.device)
+    hl_b = torch.empty_like(hl)
+    s3 = _tm_strides
+    scan_raw(u, s3(u), delta, s3(delta), A, B, s3(B), C, s3(C), D, z, s3(z), bias, softplus,
+             h0, strides2(h0), hl, strides2(hl), out, s3(out), seqlen, batch, dim, seqlen, n,
+             dtype_code(u.dtype), _stream(u),
+             pair=(split, A_b, D_b, bias_b, h0_b, hl_b, frame_len))
+    return out, hl, hl_b
+
+
+class _SelectiveScanBidir(torch.autograd.Function):
+    """:func:`_scan_bidir_forward` forward, ``selective_scan_bidir_bwd_raw`` backward, on the
+    operands :class:`_SelectiveScan` takes plus the backward direction's parameters and entry
+    state (the casts and layout changes are the caller's, as ordinary differentiable torch
+    ops)."""
+
+    @staticmethod
+    def forward(ctx, u, delta, A, B, C, D, z, bias, A_b, D_b, bias_b, h0, h0_b, split,
+                frame_len, softplus):
+        # grad mode is off in here: this is the no-grad call, same kernels, same bits
+        res = _scan_bidir_forward(u, delta, A, B, C, D, z, bias, A_b, D_b, bias_b, h0, h0_b,
+                                  split, frame_len, softplus)
+        ctx.save_for_backward(u, delta, A, B, C, D, z, bias, A_b, D_b, bias_b, h0, h0_b)
+        ctx.split, ctx.frame_len, ctx.softplus = split, frame_len, softplus
+        ctx.set_materialize_grads(False)  # an unused last state's gradient arrives as None
+        return res
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, dout, dh_last, dh_last_b):
+        u, delta, A, B, C, D, z, bias, A_b, D_b, bias_b, h0, h0_b = ctx.saved_tensors
+        batch, dim, seqlen = u.shape
+        n = A.shape[1]
+        dev = u.device
+        split = ctx.split
+
+        def tm_empty(ch):
+            return torch.empty((batch, seqlen, ch), dtype=u.dtype, device=dev).transpose(1, 2)
+
+        f32 = lambda *shape: torch.empty(shape, dtype=torch.float32, device=dev)  # noqa: E731
+        dout = tm_empty(dim).zero_() if dout is None else _channel_contig(dout.to(u.dtype))
+        if dh_last is not None:
+            dh_last = dh_last.float().contiguous()
+        if dh_last_b is not None:
+            dh_last_b = dh_last_b.float().contiguous()
+        du, ddelta, dB, dC = tm_empty(dim), tm_empty(dim), tm_empty(n), tm_empty(n)
+        dz = tm_empty(dim) if z is not None else None
+        dA, dA_b = f32(dim, n), f32(dim, n)
+        dD, dD_b = (f32(dim), f32(dim)) if D is not None else (None, None)
+        dbias, dbias_b = (f32(dim), f32(dim)) if bias is not None else (None, None)
+        # the entry states' gradients are stored only where one is asked for
+        dh0 = f32(split, dim, n) if h0 is not None and ctx.needs_input_grad[11] else None
+        dh0_b = f32(split, dim, n) if h0_b is not None and ctx.needs_input_grad[12] else None
+        s3, s2 = _tm_strides, strides2
+        st = (dim * n, n)  # every state here is (split, dim, n) fp32 contiguous
+        selective_scan_bidir_bwd_raw(
+            u, s3(u), delta, s3(delta), A, B, s3(B), C, s3(C), D, z, s3(z), bias, ctx.softplus,
+            h0, s2(h0), dout, s3(dout), dh_last, st, du, s3(du), ddelta, s3(ddelta), dz, s3(dz),
+            dB, s3(dB), dC, s3(dC), dA, dD, dbias, dh0, st, batch, dim, seqlen, n,
+            dtype_code(u.dtype), _stream(u),
+            pair=(split, A_b, D_b, bias_b, h0_b, dh_last_b, dA_b, dD_b, dbias_b, dh0_b,
+                  ctx.frame_len))
+        return (du, ddelta, dA, dB, dC, dD, dz, dbias, dA_b, dD_b, dbias_b, dh0, dh0_b,
+                None, None, None)
+
+
+def _bc_rows(t: Tensor, dtype: torch.dtype) -> Tensor:
+    """(b, n, l) B or C as the paired forward reads it: unit state stride and every row on a
+    4-byte boundary, copied where the view (e.g. columns of odd-width bf16 x_dbl rows) is not."""
+    t = _channel_contig(t.to(dtype))
+    es = t.element_size()
+    if t.data_ptr() % 4 or (t.stride(0) * es) % 4 or (t.stride(2) * es) % 4:
+        t = t.transpose(1, 2).contiguous().transpose(1, 2)
+    return t
+
+
+def selective_scan_bidir_fn(u: Tensor, delta: Tensor, A: Tensor, B: Tensor, C: Tensor,
+                            D: Optional[Tensor], z: Optional[Tensor],
+                            delta_bias: Optional[Tensor], A_b: Tensor, D_b: Optional[Tensor],
+                            delta_bias_b: Optional[Tensor], split: int, frame_len: int,
+                            initial_state: Optional[Tensor] = None,
+                            initial_state_b: Optional[Tensor] = None, *,
+                            delta_softplus: bool = True):
+    """Both directions of a bidirectional block in one scan, differentiable.  u, delta, z:
+    (2 split, d, l); B, C: (2 split, 16, l): rows [0, split) are the forward direction and
+    scan with (A, D, delta_bias, initial_state); rows [split, 2 split) are the backward
+    direction's operands already in flipped step order and scan with (A_b, D_b, delta_bias_b,
+    initial_state_b).  Returns ``(out, last_state, last_state_b)``: ``out`` (2 split, d, l) in
+    u's dtype, token-major, with the backward rows un-flipped (step t at row
+    ``t + (l - F) - 2 F (t // F)``, F = ``frame_len``; 1 = plain time reversal), and two new
+    fp32 (split, d, 16) last states, never written in place.
+
+    Forward ``vm_selective_scan_bidir_fwd``; with grad mode on and an operand that requires
+    grad, backward ``vm_selective_scan_bidir_bwd`` — one launch for both directions, which
+    reads ``out``'s gradient through the same row map.  Conventions as
+    :func:`selective_scan_fn`: casts and layout changes are differentiable torch ops outside
+    the Function, every gradient comes back in its input's dtype and shape.  Without grad it
+    is the plain paired forward."""
+    require_gpu(u, delta, A, B, C, D, z, delta_bias, A_b, D_b, delta_bias_b, initial_state,
+                initial_state_b, what="selective_scan_bidir_fn")
+    batch, dim, seqlen = u.shape
+    n = A.shape[1]
+    split, frame_len = int(split), int(frame_len)
+    if batch != 2 * split:
+        raise ValueError(f"selective_scan_bidir_fn: batch {batch} != 2 * split ({split})")
+    if n != BWD_DSTATE or A_b.shape != A.shape:
+        raise NotImplementedError(f"selective_scan_bidir_fn takes dstate == {BWD_DSTATE} in both "
+                                  f"directions, got {n} and {A_b.shape[1]}")
+    if frame_len < 1 or seqlen % frame_len:
+        raise ValueError(f"selective_scan_bidir_fn: frame_len {frame_len} must divide the "
+                         f"sequence length {seqlen}")
+    for what, a, b in (("D", D, D_b), ("delta_bias", delta_bias, delta_bias_b),
+                       ("initial_state", initial_state, initial_state_b)):
+        if (a is None) != (b is None):
+            raise ValueError(f"selective_scan_bidir_fn: {what} must be given for both "
+                             "directions or for neither")
+    dt = u.dtype
+    dtype_code(dt)
+    tm = lambda t: None if t is None else _channel_contig(t.to(dt))  # noqa: E731
+    f32 = lambda t: None if t is None else t.float().contiguous()  # noqa: E731
+    if seqlen == 0 or split == 0 or dim == 0:  # nothing to scan: the states pass through
+        zeros = lambda: torch.zeros((split, dim, n), dtype=torch.float32, device=u.device)  # noqa: E731
+        return (u.new_empty((batch, dim, seqlen)),
+                zeros() if initial_state is None else initial_state.float(),
+                zeros() if initial_state_b is None else initial_state_b.float())
+    args = (tm(u), tm(delta), f32(A), _bc_rows(B, dt), _bc_rows(C, dt), f32(D), tm(z),
+            f32(delta_bias), f32(A_b), f32(D_b), f32(delta_bias_b), f32(initial_state),
+            f32(initial_state_b), split, frame_len, bool(delta_softplus))
+    if _needs_grad(u, delta, A, B, C, D, z, delta_bias, A_b, D_b, delta_bias_b, initial_state,
+                   initial_state_b):
+        return _SelectiveScanBidir.apply(*args)
+    return _scan_bidir_forward(*args)
 
 
 def selective_state_update(state: Tensor, x: Tensor, dt: Tensor, A: Tensor, B: Tensor,

@@ -76,10 +76,11 @@ _warned_grad = False
 
 def warn_if_grad(*tensors: Optional[Tensor]) -> None:
     """The inference forward builds no autograd graph; say so once when autograd would expect
-    one.  Differentiable: the model, ``Block`` and the mixer in ``.train()`` mode without
-    ``ssm_state=`` / ``inference_params``, and ``kernels.selective_scan_fn`` /
-    ``causal_conv1d_fn`` / ``rms_norm_fn`` / ``layer_norm_fn``.  Not differentiable: anything in
-    ``.eval()`` mode, forwards that carry ``ssm_state`` at model level, and the refiner."""
+    one.  Differentiable: the model, ``Block``, the mixer and ``BiMambaRefinerBlock`` in
+    ``.train()`` mode without ``ssm_state=`` / ``inference_params``, and
+    ``kernels.selective_scan_fn`` / ``selective_scan_bidir_fn`` / ``causal_conv1d_fn`` /
+    ``rms_norm_fn`` / ``layer_norm_fn``.  Not differentiable: anything in ``.eval()`` mode and
+    forwards that carry ``ssm_state`` at model level."""
     global _warned_grad
     if _warned_grad or not torch.is_grad_enabled():
         return
@@ -87,11 +88,11 @@ def warn_if_grad(*tensors: Optional[Tensor]) -> None:
         _warned_grad = True
         warnings.warn("VideoMamba's inference forward is not differentiable: its outputs are "
                       "computed without autograd (wrap inference in torch.no_grad()).  The "
-                      "model, Block and the Mamba mixer are differentiable in .train() mode "
-                      "without ssm_state= / inference_params, and so are "
-                      "kernels.selective_scan_fn, causal_conv1d_fn, rms_norm_fn and "
-                      "layer_norm_fn; .eval() modules, model forwards that carry ssm_state "
-                      "and the refiner are not.", stacklevel=3)
+                      "model, Block, the Mamba mixer and BiMambaRefinerBlock are "
+                      "differentiable in .train() mode without ssm_state= / inference_params, "
+                      "and so are kernels.selective_scan_fn, selective_scan_bidir_fn, "
+                      "causal_conv1d_fn, rms_norm_fn and layer_norm_fn; .eval() modules and "
+                      "model forwards that carry ssm_state are not.", stacklevel=3)
 
 
 def round_up(n: int, m: int = 8) -> int:

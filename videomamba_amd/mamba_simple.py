@@ -600,20 +600,43 @@ class Mamba(nn.Module):
         path.  With ``state`` the conv continues from ``conv_state`` and the
         scan from ``ssm_state``; the returned states are new tensors attached to the graph
         (the last ``d_conv`` raw conv inputs, the scan's fp32 last state)."""
-        Bsz, L, _ = hs.shape
-        Dm, N, R, W = self.d_inner, self.d_state, self.dt_rank, self.d_conv
+        N, R = self.d_state, self.dt_rank
+        conv_state, ssm_state = self._train_states(state, hs.shape[0])
+        xz, u, x_dbl, dt, xin = self._train_front(hs, conv_state)
+        A = -torch.exp(self.A_log.float())
+        tm = lambda t: t.transpose(1, 2)  # noqa: E731  (B, L, ch) -> token-major (B, ch, L)
+        y, last = K.selective_scan_fn(
+            tm(u), tm(dt), A, tm(x_dbl[..., R:R + N]), tm(x_dbl[..., R + N:]), self.D.float(),
+            z=tm(xz[..., self.d_inner:]), delta_bias=self.dt_proj.bias.float(),
+            delta_softplus=True, initial_state=ssm_state, return_last_state=True)
+        out, new_conv = self._train_back(tm(y), xz, xin, conv_state, hs.dtype, return_state)
+        if not return_state:
+            return out
+        return out, (new_conv, last)
+
+    def _train_states(self, state: Optional[Tuple[Tensor, Tensor]], batch: int):
+        """``state`` as checked ``(conv_state, ssm_state)``, either None where absent."""
         conv_state = ssm_state = None
         if state is not None:
             conv_state, ssm_state = state
             if conv_state is not None:
-                self._check_state(conv_state, W, "conv_state", Bsz)
+                self._check_state(conv_state, self.d_conv, "conv_state", batch)
             if ssm_state is not None:
-                self._check_state(ssm_state, N, "ssm_state", Bsz)
+                self._check_state(ssm_state, self.d_state, "ssm_state", batch)
+        return conv_state, ssm_state
+
+    def _train_front(self, hs: Tensor, conv_state: Optional[Tensor]):
+        """The differentiable mixer up to the scan: in_proj -> conv + SiLU -> x_proj -> dt_proj.
+        Returns ``xz`` (B, L, 2D), ``u`` (B, L, D), ``x_dbl`` (B, L, R + 2N), ``dt`` (B, L, D;
+        its bias is added inside the scan) and the conv input ``[conv_state | x]`` where the
+        conv built it (None on the HIP conv path: :meth:`_train_back` builds it on demand)."""
+        L = hs.shape[1]
+        Dm, R, W = self.d_inner, self.dt_rank, self.d_conv
         # in_proj / out_proj: the HIP GEMM and its HIP backward where they take the shape
         # (K.linear_fn), library GEMMs under autograd otherwise
         lin = K.linear_fn if options.get().train_gemm == "hip" else F.linear
         xz = lin(hs, self.in_proj.weight, self.in_proj.bias)  # (B, L, 2D)
-        x, z = xz[..., :Dm], xz[..., Dm:]
+        x = xz[..., :Dm]
         if W <= K.CONV_BWD_MAX_WIDTH and options.get().train_ops == "hip":
             # causal depthwise conv + SiLU over [conv_state | x] on the HIP kernel and its HIP
             # backward, on the token-major view of x; the state is rounded to x's dtype first
@@ -635,20 +658,22 @@ class Mamba(nn.Module):
             u = F.silu(acc).to(x.dtype)  # (B, L, D)
         x_dbl = F.linear(u, self.x_proj.weight, self.x_proj.bias)  # (B, L, R + 2N)
         dt = F.linear(x_dbl[..., :R], self.dt_proj.weight)  # bias added inside the scan
-        A = -torch.exp(self.A_log.float())
-        tm = lambda t: t.transpose(1, 2)  # noqa: E731  (B, L, ch) -> token-major (B, ch, L)
-        y, last = K.selective_scan_fn(
-            tm(u), tm(dt), A, tm(x_dbl[..., R:R + N]), tm(x_dbl[..., R + N:]), self.D.float(),
-            z=tm(z), delta_bias=self.dt_proj.bias.float(), delta_softplus=True,
-            initial_state=ssm_state, return_last_state=True)
-        out = lin(tm(y), self.out_proj.weight, self.out_proj.bias)
+        return xz, u, x_dbl, dt, xin
+
+    def _train_back(self, y: Tensor, xz: Tensor, xin: Optional[Tensor],
+                    conv_state: Optional[Tensor], in_dtype: torch.dtype, return_state: bool):
+        """The differentiable mixer after the scan: out_proj of ``y`` (B, L, D) and, with
+        ``return_state``, the new conv state (the last ``d_conv`` raw conv inputs, in the given
+        conv state's dtype or ``in_dtype``; else None)."""
+        lin = K.linear_fn if options.get().train_gemm == "hip" else F.linear
+        out = lin(y, self.out_proj.weight, self.out_proj.bias)
         if not return_state:
-            return out
-        cs_dtype = conv_state.dtype if conv_state is not None else hs.dtype
+            return out, None
+        cs_dtype = conv_state.dtype if conv_state is not None else in_dtype
         if xin is None:
-            xin = self._conv_input(x, conv_state)
-        new_conv = xin[:, -W:].transpose(1, 2).to(cs_dtype)  # the last d_conv raw inputs
-        return out, (new_conv, last)
+            xin = self._conv_input(xz[..., :self.d_inner], conv_state)
+        new_conv = xin[:, -self.d_conv:].transpose(1, 2).to(cs_dtype)  # the last d_conv raw inputs
+        return out, new_conv
 
     def _conv_input(self, x: Tensor, conv_state: Optional[Tensor]) -> Tensor:
         """[left context | x] as (B, d_conv + L, D) in x's dtype: the conv state, or zeros."""

@@ -108,6 +108,14 @@ documented options object; tests and sweeps change them with :func:`override`.
                      than "hip" at B = 8 and 32).
                      x_proj, dt_proj and the patch embed are library GEMMs either way.  The
                      inference path never reads it.
+    train_refiner    how BiMambaRefinerBlock runs its differentiable path.  "paired": one
+                     selective_scan_bidir_fn call for both directions (forward
+                     vm_selective_scan_bidir_fwd, backward vm_selective_scan_bidir_bwd — one
+                     scan-backward launch over the 2 B rows) wherever the paired kernels take
+                     the configuration, else as "blocks"; "blocks": the reference's composition
+                     on the differentiable Block, two scan-backward launches of B rows each.
+                     The default is the one scripts/bench_train_bwd.py --compare refiner
+                     measured faster.  The inference path never reads it.
 
 Options are process-global (not thread-local): the model is driven from one host thread,
 and the sub-batch issue threads of ``batch_stream_lock`` read the caller's options.
@@ -148,6 +156,7 @@ class Options:
     small_gemm_max_n: int = 1024
     train_ops: str = "hip"
     train_gemm: str = "hip"
+    train_refiner: str = "paired"
 
     def validate(self) -> None:
         if self.mixer_layout not in _LAYOUTS:
@@ -166,6 +175,8 @@ class Options:
             raise ValueError(f"train_ops must be hip / torch, got {self.train_ops!r}")
         if self.train_gemm not in ("hip", "library"):
             raise ValueError(f"train_gemm must be hip / library, got {self.train_gemm!r}")
+        if self.train_refiner not in ("paired", "blocks"):
+            raise ValueError(f"train_refiner must be paired / blocks, got {self.train_refiner!r}")
         if self.gemm_tuning not in _TUNING:
             raise ValueError(f"gemm_tuning must be one of {_TUNING}, got {self.gemm_tuning!r}")
 

@@ -22,6 +22,14 @@ Configurations the paired kernels do not take (d_state != 16, forward / backward
 different geometry, widths the fused norm rejects, odd bf16 x_dbl rows, unaligned input)
 run the reference's composition instead — the forward block, the backward block on a
 flipped copy, the flip back and the gate — on the same per-block HIP kernels.
+
+In ``.train()`` mode with autograd on (``Block``'s gate) the block is differentiable
+(``options.train_refiner``): "paired" runs the per-direction add + norm and mixer fronts under
+autograd and ONE ``kernels.selective_scan_bidir_fn`` call over the 2B rows, whose backward is one
+``vm_selective_scan_bidir_bwd`` launch that reads the backward direction's ``dout`` through the
+forward's row map — so neither y nor its gradient is flipped; "blocks" is the reference's
+composition on the differentiable ``Block``.  Everything above is the inference path and is
+what runs otherwise.
 """
 
 from __future__ import annotations
@@ -33,8 +41,9 @@ import torch.nn as nn
 from torch import Tensor
 
 from . import kernels as K
+from . import options
 from .layers import round_up, warn_if_grad
-from .mamba_simple import _linear_into
+from .mamba_simple import _linear_into, takes_training_path
 from .videomamba import Block, _norm_kind, create_block
 
 LayerState = Tuple[Tensor, Tensor]
@@ -82,9 +91,21 @@ class BiMambaRefinerBlock(nn.Module):
 
     def forward(self, x: Tensor, state_fwd: Optional[LayerState] = None,
                 state_bwd_init: Optional[LayerState] = None, use_checkpoint: bool = False):
+        """x: (B, L, C) or (B, T, N, C) -> (out, new forward state).  In ``.train()`` mode with
+        autograd on (``Block``'s gate, ``takes_training_path``) the block is differentiable:
+        gradients reach every parameter, ``x`` and the states, which are read and never
+        modified, and the returned forward state is new tensors attached to the graph
+        (:meth:`_forward_train`).  Otherwise it runs without autograd and updates the ssm
+        states in place, as the inference path always has.  ``use_checkpoint`` is accepted
+        for API parity (activations are not recomputed)."""
         seq, packed = self._pack_tokens(x)
         bsz = seq.shape[0]
         K.require_gpu(seq, what="BiMambaRefinerBlock")
+        if takes_training_path(self, seq, *(state_fwd or ()), *(state_bwd_init or ())):
+            st_f = self._ensure_state(self.block_fwd, state_fwd, bsz, seq.device)
+            st_b = self._ensure_state(self.block_bwd, state_bwd_init, bsz, seq.device)
+            out, new_f = self._forward_train(seq, packed, st_f, st_b)
+            return self._unpack_tokens(out, packed), new_f
         warn_if_grad(seq, self.block_fwd.mixer.in_proj.weight)
         st_f = self._ensure_state(self.block_fwd, state_fwd, bsz, seq.device)
         st_b = self._ensure_state(self.block_bwd, state_bwd_init, bsz, seq.device)
@@ -111,16 +132,66 @@ class BiMambaRefinerBlock(nn.Module):
                 and ((mf.dt_rank + 2 * mf.d_state) * es) % 4 == 0
                 and (not seq.is_contiguous() or seq.data_ptr() % 16 == 0))
 
+    @staticmethod
+    def _flip(t: Tensor, packed) -> Tensor:
+        """(B, L, C) reversed in time: whole frames for packed 4-D input (``:61-68``)."""
+        if packed is None:
+            return torch.flip(t, dims=[1])
+        b, tt, n = packed
+        return torch.flip(t.reshape(b, tt, n, t.shape[-1]), dims=[1]).reshape(b, tt * n, -1)
+
+    def _forward_train(self, seq: Tensor, packed, st_f: LayerState, st_b: LayerState):
+        """The differentiable block, by ``options.train_refiner``.  "blocks": the reference's
+        composition (:meth:`_forward_blocks`) on the differentiable ``Block`` — any
+        configuration its training path takes; ``d_state != 16`` raises the mixer's
+        ``NotImplementedError``.  "paired": both directions through one
+        ``K.selective_scan_bidir_fn`` call where the two mixers have one geometry with 16
+        states, else as "blocks"."""
+        mf, mb = self.block_fwd.mixer, self.block_bwd.mixer
+        same = all(getattr(mf, a) == getattr(mb, a)
+                   for a in ("d_inner", "d_state", "dt_rank", "d_conv"))
+        if (options.get().train_refiner == "paired" and same and mf.d_state == K.BWD_DSTATE
+                and seq.shape[1] > 0):
+            return self._forward_train_paired(seq, packed, st_f, st_b)
+        return self._forward_blocks(seq, packed, st_f, st_b)
+
+    def _forward_train_paired(self, seq: Tensor, packed, st_f: LayerState, st_b: LayerState):
+        """Per direction the add + norm (the backward one on a flipped copy of ``seq``, a
+        C-wide torch copy) and the mixer front; the two directions' u, dt, z and x_dbl
+        concatenated along batch (three d_inner-wide copies); one paired scan, whose output
+        comes back with the backward rows un-flipped — so neither y nor its gradient is ever
+        flipped — and whose backward is one launch over the 2 B rows; per-direction out_proj;
+        the gate and the Linear as torch ops."""
+        bf, bb = self.block_fwd, self.block_bwd
+        mf, mb = bf.mixer, bb.mixer
+        B = seq.shape[0]
+        Dm, N, R = mf.d_inner, mf.d_state, mf.dt_rank
+        conv_f, ssm_f = mf._train_states(st_f, B)
+        conv_b, ssm_b = mb._train_states(st_b, B)
+        hn_f, _ = bf._add_norm(seq, None)
+        hn_b, _ = bb._add_norm(self._flip(seq, packed), None)
+        xz_f, u_f, xd_f, dt_f, xin_f = mf._train_front(hn_f, conv_f)
+        xz_b, u_b, xd_b, dt_b, _ = mb._train_front(hn_b, conv_b)
+        cat = lambda a, b: torch.cat([a, b], dim=0)  # noqa: E731
+        tm = lambda t: t.transpose(1, 2)  # noqa: E731  (2B, L, ch) -> token-major (2B, ch, L)
+        x_dbl = cat(xd_f, xd_b)
+        y, last_f, _ = K.selective_scan_bidir_fn(
+            tm(cat(u_f, u_b)), tm(cat(dt_f, dt_b)), -torch.exp(mf.A_log.float()),
+            tm(x_dbl[..., R:R + N]), tm(x_dbl[..., R + N:]), mf.D.float(),
+            tm(cat(xz_f[..., Dm:], xz_b[..., Dm:])), mf.dt_proj.bias.float(),
+            -torch.exp(mb.A_log.float()), mb.D.float(), mb.dt_proj.bias.float(), B,
+            1 if packed is None else packed[2], initial_state=ssm_f, initial_state_b=ssm_b)
+        y = tm(y)  # (2B, L, D): rows [B, 2B) already in the sequence's own order
+        out_f, new_conv = mf._train_back(y[:B], xz_f, xin_f, conv_f, hn_f.dtype, True)
+        out_b, _ = mb._train_back(y[B:], xz_b, None, conv_b, hn_b.dtype, False)
+        gate = self.fusion_gate(torch.cat([out_f, out_b], dim=-1))
+        return self.out_proj(gate * out_f + (1.0 - gate) * out_b), (new_conv, last_f)
+
     def _forward_blocks(self, seq: Tensor, packed, st_f: LayerState, st_b: LayerState):
         """The reference's composition (``refiner_backbone.py:98-135``) on the per-block
         HIP path: forward block, backward block over the time-flipped sequence (frame order
         flipped for 4-D input, ``:61-68``), flip back, sigmoid gate, Linear."""
-        def flip(t: Tensor) -> Tensor:
-            if packed is None:
-                return torch.flip(t, dims=[1])
-            b, tt, n = packed
-            return torch.flip(t.reshape(b, tt, n, t.shape[-1]), dims=[1]).reshape(b, tt * n, -1)
-
+        flip = lambda t: self._flip(t, packed)  # noqa: E731
         out_f, _, new_f = self.block_fwd(seq, state=st_f, return_state=True)
         out_b_rev, _, _ = self.block_bwd(flip(seq), state=st_b, return_state=True)
         out_b = flip(out_b_rev)

@@ -538,7 +538,8 @@ long long vm_add_norm_bwd_workspace_bytes(long long rows, int cols);
  * [0, rows) of x (+ residual) at x + b*in_batch_stride are normalised into out + b *
  * out_batch_stride (rows contiguous).  rev_frame > 0 reads rows [head, rows) in reversed
  * frame order (frames of rev_frame rows, row order kept within a frame): the flipped
- * input of BiMambaRefinerBlock's backward block (models/refiner_backbone.py:98-135).  Rows [0, head) (the CLS row) are only normalised;
+ * input of BiMambaRefinerBlock's backward block (models/refiner_backbone.py:98-135).  Rows [0, head) (the CLS row) are only normalised,
+ * for any head <= rows (more than one 16-row slice of them takes more workgroups, not another call);
  * rows [head, rows) form `groups` pooling groups: equal groups of `group_rows` rows when
  * bounds == NULL (head + groups*group_rows == rows, max_group_rows == group_rows), else
  * bounds (batch, groups+1) int32 row bounds with bounds[b][0] == head and

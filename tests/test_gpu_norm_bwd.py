@@ -4,7 +4,8 @@ for gradients stored in fp32 (dweight, dbias, fp32 dx / dresidual), 2e-2 for gra
 in bf16 against the reference rounded once to bf16 — the scan backward's bounds.
 
 Shapes: rows 1, 5, 257 (one short workgroup, two, 65 with a one-row tail); cols 64, 100 (the
-non-vector form), 192, 576 (VideoMamba-M); RMSNorm and LayerNorm; bias on and off (LayerNorm);
+backward's non-vector form; the forward vectorises it), 192, 576 (VideoMamba-M); RMSNorm and
+LayerNorm; bias on and off (LayerNorm);
 residual none / fp32 / bf16; ``prenorm`` off, on, and on with a gradient arriving at
 ``residual_out``; x in fp32 and bf16; one bf16 case with ``residual_in_fp32=False`` and no
 residual, so the saved sum is bf16.  The product is thinned by cycling the other axes along

@@ -6,6 +6,8 @@
 // One wave per row; each lane keeps its strided slice of the row in registers, so the
 // row is read once and written once (HBM-bound: 12 B/elem at bf16 x, fp32 residual).
 
+#include <algorithm>
+
 #include "vm_common.h"
 
 namespace vm {
@@ -277,9 +279,10 @@ __global__ __launch_bounds__(256) void norm_pool_rows_kernel(const NormPoolParam
   const int b = blockIdx.z, gy = blockIdx.y, s = blockIdx.x;
   const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
   int lo, hi;
-  if (gy == 0) {
-    if (s) return;
+  if (gy == 0) {  // the head: slice s of its rows (the grid has ceil(head / kPoolRB) of them)
     lo = 0; hi = p.head;
+  } else if (s >= p.slices) {
+    return;       // a head longer than the longest group widens the grid
   } else if (p.bounds) {
     lo = p.bounds[(long long)b * (p.groups + 1) + gy - 1];
     hi = p.bounds[(long long)b * (p.groups + 1) + gy];
@@ -378,9 +381,10 @@ __global__ __launch_bounds__(256) void norm_pool_rows_bf16_kernel(const NormPool
   const int b = blockIdx.z, gy = blockIdx.y, s = blockIdx.x;
   const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
   int lo, hi;
-  if (gy == 0) {
-    if (s) return;
+  if (gy == 0) {  // the head: slice s of its rows (the grid has ceil(head / kPoolRB) of them)
     lo = 0; hi = p.head;
+  } else if (s >= p.slices) {
+    return;       // a head longer than the longest group widens the grid
   } else if (p.bounds) {
     lo = p.bounds[(long long)b * (p.groups + 1) + gy - 1];
     hi = p.bounds[(long long)b * (p.groups + 1) + gy];
@@ -671,7 +675,8 @@ extern "C" int vm_norm_pool_fwd(const void* x, int x_dtype, const void* residual
   p.head = head; p.groups = groups; p.group_rows = group_rows; p.bounds = bounds;
   p.slices = max_group_rows > 0 ? (max_group_rows + kPoolRB - 1) / kPoolRB : 1;
   p.part = static_cast<float*>(workspace);
-  dim3 grid(p.slices, groups + 1, batch);
+  // x: the kPoolRB-row slices of a group, or of the head rows where those are more
+  dim3 grid(std::max(p.slices, (head + kPoolRB - 1) / kPoolRB), groups + 1, batch);
   const size_t lds = 4 * cols * sizeof(float);
   hipStream_t s = static_cast<hipStream_t>(stream);
   const int cpl = (cols + 255) / 256;

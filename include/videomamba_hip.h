@@ -547,6 +547,12 @@ long long vm_add_norm_bwd_workspace_bytes(long long rows, int cols);
  * workspace (>= vm_norm_pool_workspace_bytes) the fp32 column sums of the rounded outputs
  * of each group are written there for vm_pool_finish_fwd; NULL skips them.
  * cols % 4 == 0, cols <= 2048, 16-byte aligned x / residual / out / weight.
+ *
+ * vm_norm_pool_workspace_bytes: 4 * batch * groups * slices * cols with
+ * slices = max(1, ceil(max_group_rows / 16)), -1 for a negative argument.  Every group owns at
+ * least one slice: for max_group_rows == 0 (a head-only call) the answer is
+ * 4 * batch * groups * cols, not 0, the forward writes zeros there, and a non-NULL workspace
+ * smaller than that is refused (VM_E_INVALID) like any other that is below the query.
  */
 long long vm_norm_pool_workspace_bytes(int batch, int groups, int max_group_rows, int cols);
 int vm_norm_pool_fwd(const void* x, int x_dtype, const void* residual, int res_dtype,

@@ -266,7 +266,8 @@ VARIANTS = {
     "cp_occ2": [("vm_conv_proj.hip", "dim3(pl.main.block), pl.main.lds, st, p);",
                  "dim3(pl.main.block), pl.main.lds + 30000, st, p);")],
     # final norm + pooling through the dtype-generic rows kernel only
-    "np_generic": [("vm_norm.hip", "constexpr bool kPoolFast = true;", "constexpr bool kPoolFast = false;")],
+    "np_generic": [("vm_norm_plan.h", "  const bool fast = in.x_dtype == kNormBf16 && in.out_dtype == kNormBf16 &&",
+                    "  const bool fast = false && in.x_dtype == kNormBf16 && in.out_dtype == kNormBf16 &&")],
     "ldma16_i128x128": [("vm_gemm_plan.h", "constexpr DmaTile kDmaWide{128, 128, 2, 4};",
                          "constexpr DmaTile kDmaWide{128, 128, 2, 8};")],
     "ldma8_i64x128": [("vm_gemm_plan.h", "constexpr DmaTile kDmaWide{128, 128, 2, 4};",

@@ -21,9 +21,12 @@ References (float64 on the stored input values; bf16 inputs are upcast, never re
 
 Dispatch
     :func:`add_norm_instance` and :func:`pool_instance` restate which kernel instance
-    ``vm_add_norm_fwd`` / ``vm_norm_pool_fwd`` launch (``vm_norm.hip``: ``vec``, the fast path,
-    ``cpl``, ``vpl``, write-through); ``ADD_NORM_INSTANCES`` (28) and ``POOL_INSTANCES`` (8) list
-    every one, and the CPU test asserts the case tables reach them all.
+    ``vm_add_norm_fwd`` / ``vm_norm_pool_fwd`` launch (``vm_norm_plan.h``: ``vec``, the fast
+    path, ``cpl``, ``vpl``, write-through); ``ADD_NORM_INSTANCES`` (28) and ``POOL_INSTANCES`` (8)
+    list every one, and the CPU test asserts the case tables reach them all.  The restatement is
+    the tests' own; ``plan_line`` gives a case as ``tests/host/norm_fwd_instance_of.cpp`` reads
+    it, and the CPU test holds every case's restated instance to the one the library's planner
+    names (``SMALL_STORE_ROWS`` and ``POOL_RB`` to the header's values likewise).
 
 Comparator
     ``train_bwd_ref.tol_and_ref`` / ``assert_within_rms``: ``|got - ref| <= tol (rms(ref) +
@@ -49,12 +52,13 @@ from train_bwd_ref import assert_within_rms, tol_and_ref  # noqa: F401  (re-expo
 
 F32, BF16, F64 = torch.float32, torch.bfloat16, torch.float64
 EPS = 1e-5
-SMALL_STORE_ROWS = 32768   # kSmallStoreRows (vm_common.h): the write-through switch
-POOL_RB = 16               # kPoolRB (vm_norm.hip): rows of one pooling slice
+SMALL_STORE_ROWS = 32768   # kSmallStoreRows (vm_norm_plan.h): the write-through switch
+POOL_RB = 16               # kPoolRB (vm_norm_plan.h): rows of one pooling slice
 MARGIN = 4096              # sentinel bytes on either side of a guarded tensor
 
 _name = lambda dt: {None: "none", F32: "fp32", BF16: "bf16", F64: "fp64"}[dt]  # noqa: E731
 _other = lambda dt: BF16 if dt == F32 else F32  # noqa: E731
+_code = lambda dt: 1 if dt == BF16 else 0  # noqa: E731  (VM_DTYPE_BF16 / VM_DTYPE_F32)
 
 
 def f64(t: Optional[torch.Tensor]) -> Optional[torch.Tensor]:
@@ -125,6 +129,16 @@ class NormCase(NamedTuple):
         return (f"r{self.rows}-c{self.cols}-{'rms' if self.rms else 'ln'}"
                 f"{'-bias' if self.bias else ''}-x{_name(self.x)}-y{_name(self.out)}-"
                 f"res{_name(self.res)}-ro{self.ro}{'-off%d' % self.offset if self.offset else ''}")
+
+    def plan_line(self) -> str:
+        """The case as ``tests/host/norm_fwd_instance_of.cpp`` reads it (kind 1): rows, cols,
+        is_rms, bias, x / out dtype codes, residual and residual_out presence and dtype codes,
+        and whether ``x`` is 16-byte aligned (every other buffer is)."""
+        rod = self.ro_dtype
+        x_al = (self.offset * (2 if self.x == BF16 else 4)) % 16 == 0
+        return " ".join(str(int(v)) for v in (
+            1, self.rows, self.cols, self.rms, self.bias, _code(self.x), _code(self.out),
+            self.res is not None, _code(self.res), rod is not None, _code(rod), x_al))
 
 
 def add_norm_instance(c: NormCase) -> tuple:
@@ -291,6 +305,17 @@ class PoolCase(NamedTuple):
                 f"{'-rev%d' % self.rev_frame if self.rev_frame else ''}"
                 f"{'-sums' if self.sums else ''}")
 
+    def plan_line(self) -> str:
+        """The case as ``tests/host/norm_fwd_instance_of.cpp`` reads it (kind 2): batch, rows,
+        cols, head, groups, group_rows, max_group_rows, bounds given, x / out dtype codes,
+        residual presence and dtype code, rev_frame and the two batch strides of the GPU test's
+        padded buffers."""
+        return " ".join(str(int(v)) for v in (
+            2, POOL_BATCH, self.rows, self.cols, self.head, self.groups,
+            self.sizes[0][0] if self.implicit else 0, self.mgr, not self.implicit, _code(self.x),
+            _code(self.out), self.res is not None, _code(self.res), self.rev_frame,
+            (self.rows + POOL_PAD_ROWS) * self.cols, (self.rows + POOL_OUT_PAD) * self.cols))
+
 
 def pool_instance(c: PoolCase) -> tuple:
     """("fast", CPL) for ``norm_pool_rows_bf16_kernel``, ("generic", CPL) for
@@ -354,6 +379,9 @@ def _pool_cases() -> List[PoolCase]:
 
 
 POOL_CASES = _pool_cases()
+# Head rows only: two implicit groups of no rows (max_group_rows 0).  Each group still owns one
+# slice of the workspace, which the forward fills with zeros.
+HEAD_ONLY = PoolCase(64, BF16, BF16, F32, True, False, 3, ((0, 0),) * POOL_BATCH, True, 0, 0, True)
 POOL_PAD_ROWS = 2    # rows of h past `rows` (in_batch_stride padding)
 POOL_OUT_PAD = 3     # sentinel rows of out past `rows` in every batch row
 

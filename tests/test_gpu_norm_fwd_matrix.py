@@ -18,7 +18,8 @@ cases are larger than 32769 x 8: ``add_rms_bf16_kernel<CPL, true, true>`` withou
 exists for CPL 2, 3, 4 only above 32768 rows, so 32769 x 260 / 516 / 772 run once each, with
 the float64 reference on their first and last 261 rows and the vector kernel's bits on all.
 Norm + pool: batch 2, head 0 to 17, groups either side of the 16-row slice, unequal ``bounds``,
-``rev_frame``, padded batch strides in and out.  Pool finish: cols 4 to 2048, 1 / 5 / 13
+``rev_frame``, padded batch strides in and out, and one head-only call (two groups of no rows)
+on a workspace of exactly the query's size.  Pool finish: cols 4 to 2048, 1 / 5 / 13
 slices, all four modes.  Steps: batch 1 / 3, D 1 / 24 / 257, N 1 / 16 / 17, W 1 to 8.
 
 A head of more than 16 rows (``h17`` cases) left rows [16, head) of the features unwritten
@@ -236,6 +237,39 @@ def test_norm_pool_refusals_write_nothing(what):
     assert _raw_norm_pool(x, out.t, rows, cols, head, groups, gr, w) == VM_E_INVALID
     torch.cuda.synchronize()
     assert out.unchanged()
+
+
+def test_head_only_norm_pool_stays_inside_the_workspace_the_query_sizes():
+    """Head rows only (rows = head = 3, two implicit groups of no rows, max_group_rows 0) with
+    sums requested: the query sizes one slice per group, the forward fills exactly that region
+    with zeros and leaves both margins alone, and the features match float64 as elsewhere.  The
+    same call with one byte less of workspace is refused and writes nothing.  (The query used
+    to answer 0 bytes here while every group block stored cols floats.)"""
+    c = nm.HEAD_ONLY
+    assert c.rows == c.head == 3 and c.groups == 2 and c.mgr == 0 and c.slices == 1
+    nbytes = K.norm_pool_workspace_bytes(nm.POOL_BATCH, c.groups, 0, c.cols)
+    assert nbytes == 4 * nm.POOL_BATCH * c.groups * c.cols
+    ops = nm.pool_inputs(c)
+    out, ws = _launch_norm_pool(c, ops)
+    assert out.intact(), "out: a sentinel (margin or padding row) was overwritten"
+    assert ws.intact(), "workspace: sentinel margin overwritten"
+    assert ws.nbytes == nbytes and bool((ws.t == 0).all()), "the empty groups' sums are not zeros"
+    worst = {}
+    _check(out.t, nm.norm_pool_ref64(ops, c), "features", worst)
+    _report("norm_pool", c.id + " " + str(nm.pool_instance(c)), worst)
+    # one byte less: refused, nothing written
+    x, res, w = _dev(ops["x"]), _dev(ops["residual"]), _dev(ops["weight"])
+    out2 = nm.Guarded((nm.POOL_BATCH, c.rows, c.cols), c.out, DEV)
+    ws2 = nm.Guarded((nm.POOL_BATCH, c.groups, 1, c.cols), F32, DEV)
+    lib = _lib.load()
+    rc = lib.vm_norm_pool_fwd(
+        x.data_ptr(), K.dtype_code(x.dtype), res.data_ptr(), K.dtype_code(res.dtype), x.stride(0),
+        w.data_ptr(), None, EPS, 1, out2.t.data_ptr(), K.dtype_code(c.out), out2.t.stride(0),
+        nm.POOL_BATCH, c.rows, c.cols, c.head, c.groups, 0, None, 0, 0, ws2.t.data_ptr(),
+        nbytes - 1, _stream())
+    torch.cuda.synchronize()
+    assert rc == VM_E_INVALID and b"workspace smaller" in lib.vm_last_error()
+    assert out2.unchanged() and ws2.unchanged()
 
 
 # --------------------------------------------------------------------------- c. pool finish

@@ -1,7 +1,13 @@
 """Keeps the norm forward / norm + pool / one-token step matrix honest without a GPU: the
 float64 references against torch and the oracle, the pooling reference against a direct
-restatement of the model's pooling, the sentinel helper, and the case tables' coverage — every
-value of every axis, every kernel instance of the two dispatchers."""
+restatement of the model's pooling, the sentinel helper, the case tables' coverage — every
+value of every axis, every kernel instance of the two dispatchers — and the host plan itself
+(vm_norm_plan.h): walked by a stand-alone program under ASan + UBSan, and asked for the instance
+of every case, which must be the one the tests' own restatement names."""
+
+import os
+import shutil
+import subprocess
 
 import pytest
 import torch
@@ -11,6 +17,7 @@ import norm_fwd_matrix as nm
 from oracle import videomamba_oracle as orc
 
 F32, BF16, F64 = torch.float32, torch.bfloat16, torch.float64
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 
 # --------------------------------------------------------------------------- references
@@ -325,3 +332,58 @@ def test_step_cases_cover_every_axis_value():
     for w in nm.STEP_W:
         assert {c.silu for c in conv if c.width == w} == {True, False}, w
     assert len({c.id for c in cases}) == len(cases) and len({c.id for c in conv}) == len(conv)
+
+
+# --------------------------------------------------------------------------- the host plan
+def _host_program(tmp_path, name):
+    """tests/host/<name>.cpp built as a program of its own with the host compiler under
+    ASan + UBSan; nothing is loaded into Python."""
+    rocm_clang = "/opt/rocm/llvm/bin/clang++"
+    cxx = [rocm_clang] if os.path.exists(rocm_clang) else \
+        [shutil.which("g++") or "g++", "-static-libasan", "-static-libubsan"]
+    exe = str(tmp_path / name)
+    subprocess.run(cxx + ["-std=c++17", "-O1", "-g", "-fsanitize=address,undefined",
+                          "-fno-sanitize-recover=all", "-I",
+                          os.path.join(ROOT, "videomamba_amd", "csrc"),
+                          os.path.join(ROOT, "tests", "host", name + ".cpp"), "-o", exe],
+                   check=True, timeout=120)
+    return exe
+
+
+def test_norm_fwd_plan_check_program_passes_under_sanitizers(tmp_path):
+    """tests/host/norm_fwd_plan_check.cpp walks plan_add_norm, plan_norm_pool and
+    plan_pool_finish over their grids and exits non-zero on a cpl / vpl that is not the smallest
+    of its family's set, a fast family chosen off its documented conditions, a grid that misses
+    rows, part regions that overlap, leave a gap or end off workspace_bytes (max_group_rows == 0
+    included), a query that differs from the plan, a refusal out of order or a 2^31 switch at
+    another row count."""
+    run = subprocess.run([_host_program(tmp_path, "norm_fwd_plan_check")], capture_output=True,
+                         text=True, timeout=120)
+    assert run.returncode == 0, run.stdout + run.stderr
+    assert " 0 failures" in run.stdout
+
+
+def test_every_case_reaches_the_instance_the_plan_names(tmp_path):
+    """tests/host/norm_fwd_instance_of.cpp feeds every case's plan input to plan_add_norm /
+    plan_norm_pool and prints the instance: it must be the one add_norm_instance /
+    pool_instance restate, all 28 + 8 instances must appear in the program's own output, and
+    the two constants the tables are built around must be the header's."""
+    exe = _host_program(tmp_path, "norm_fwd_instance_of")
+    pools = nm.POOL_CASES + [nm.HEAD_ONLY]
+    text = "0\n" + "".join(c.plan_line() + "\n" for c in nm.NORM_CASES + pools)
+    run = subprocess.run([exe], input=text, capture_output=True, text=True, timeout=120)
+    assert run.returncode == 0, run.stdout + run.stderr
+    got = [ln.split() for ln in run.stdout.splitlines()]
+    assert len(got) == 1 + len(nm.NORM_CASES) + len(pools)
+    assert got[0] == ["consts", str(nm.SMALL_STORE_ROWS), str(nm.POOL_RB)]
+    norm_got = [(g[0], int(g[1])) + tuple(bool(int(v)) for v in g[2:])
+                for g in got[1:1 + len(nm.NORM_CASES)]]
+    wrong = [(c.id, g) for c, g in zip(nm.NORM_CASES, norm_got) if g != nm.add_norm_instance(c)]
+    assert not wrong, wrong[:8]
+    assert set(norm_got) == set(nm.ADD_NORM_INSTANCES) and len(set(norm_got)) == 28
+    pool_got = [(g[0], int(g[1]), int(g[2])) for g in got[1 + len(nm.NORM_CASES):]]
+    wrong = [(c.id, g) for c, g in zip(pools, pool_got)
+             if g != nm.pool_instance(c) + (c.slices,)]
+    assert not wrong, wrong[:8]
+    assert {g[:2] for g in pool_got} == set(nm.POOL_INSTANCES) and len(nm.POOL_INSTANCES) == 8
+    assert pool_got[-1] == ("fast", 1, 1)     # the head-only case: one slice per empty group

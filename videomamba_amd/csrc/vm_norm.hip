@@ -6,11 +6,12 @@
 // One wave per row; each lane keeps its strided slice of the row in registers, so the
 // row is read once and written once (HBM-bound: 12 B/elem at bf16 x, fp32 residual).
 
-#include <algorithm>
-
 #include "vm_common.h"
+#include "vm_norm_plan.h"
 
 namespace vm {
+
+static_assert(kNormF32 == VM_DTYPE_F32 && kNormBf16 == VM_DTYPE_BF16, "vm_norm_plan.h dtype codes");
 
 struct NormParams {
   const void* x; const void* res; const float* w; const float* bias; void* out; void* res_out;
@@ -23,11 +24,22 @@ __device__ __forceinline__ float wave_sum(float v) {
   return v;
 }
 
+// four bf16 in two dwords (element 0 in the low half of `lo`) <-> four floats
+__device__ __forceinline__ void unpack_bf16x4(uint32_t lo, uint32_t hi, float (&v)[4]) {
+  v[0] = __uint_as_float(lo << 16); v[1] = __uint_as_float(lo & 0xffff0000u);
+  v[2] = __uint_as_float(hi << 16); v[3] = __uint_as_float(hi & 0xffff0000u);
+}
+__device__ __forceinline__ uint2 pack_bf16x4(const float (&v)[4]) {
+  uint2 q;
+  q.x = static_cast<uint32_t>(from_f32<bf16_t>(v[0])) | (static_cast<uint32_t>(from_f32<bf16_t>(v[1])) << 16);
+  q.y = static_cast<uint32_t>(from_f32<bf16_t>(v[2])) | (static_cast<uint32_t>(from_f32<bf16_t>(v[3])) << 16);
+  return q;
+}
+
 __device__ __forceinline__ void load4_dyn(const void* p, long long i, int dtype, float (&v)[4]) {
   if (dtype == VM_DTYPE_BF16) {
     const uint2 q = *reinterpret_cast<const uint2*>(static_cast<const bf16_t*>(p) + i);
-    v[0] = __uint_as_float(q.x << 16); v[1] = __uint_as_float(q.x & 0xffff0000u);
-    v[2] = __uint_as_float(q.y << 16); v[3] = __uint_as_float(q.y & 0xffff0000u);
+    unpack_bf16x4(q.x, q.y, v);
   } else {
     const float4 q = *reinterpret_cast<const float4*>(static_cast<const float*>(p) + i);
     v[0] = q.x; v[1] = q.y; v[2] = q.z; v[3] = q.w;
@@ -35,10 +47,7 @@ __device__ __forceinline__ void load4_dyn(const void* p, long long i, int dtype,
 }
 __device__ __forceinline__ void store4_dyn(void* p, long long i, int dtype, const float (&v)[4]) {
   if (dtype == VM_DTYPE_BF16) {
-    uint2 q;
-    q.x = static_cast<uint32_t>(from_f32<bf16_t>(v[0])) | (static_cast<uint32_t>(from_f32<bf16_t>(v[1])) << 16);
-    q.y = static_cast<uint32_t>(from_f32<bf16_t>(v[2])) | (static_cast<uint32_t>(from_f32<bf16_t>(v[3])) << 16);
-    *reinterpret_cast<uint2*>(static_cast<bf16_t*>(p) + i) = q;
+    *reinterpret_cast<uint2*>(static_cast<bf16_t*>(p) + i) = pack_bf16x4(v);
   } else {
     *reinterpret_cast<float4*>(static_cast<float*>(p) + i) = make_float4(v[0], v[1], v[2], v[3]);
   }
@@ -59,6 +68,22 @@ __device__ __forceinline__ __amdgpu_buffer_rsrc_t norm_row_rsrc(const void* base
   void* ub = reinterpret_cast<void*>((static_cast<uint64_t>(hi) << 32) | lo);
   return __builtin_amdgcn_make_buffer_rsrc(ub, 0, bytes, 0x00020000);
 }
+// Byte offset of a lane's chunk j (elements of `es` bytes) in its row's buffer, past the range
+// for a chunk past `cols`.
+__device__ __forceinline__ int norm_chunk_off(int lane, int j, int cols, int es) {
+  int o = lane * 4 + 256 * j < cols ? (lane * 4 + 256 * j) * es : kNormOut;
+  asm volatile("" : "+v"(o));  // a select, not a branch around the access
+  return o;
+}
+typedef __attribute__((__vector_size__(4 * sizeof(float)))) float v4f;
+typedef __attribute__((__vector_size__(2 * sizeof(int)))) int v2i;
+// four floats rounded to bf16 into 8 bytes of a row buffer (AUX: the store policy)
+template <int AUX>
+__device__ __forceinline__ void store_bf16x4(const float (&y)[4], __amdgpu_buffer_rsrc_t r, int off) {
+  const uint2 q = pack_bf16x4(y);
+  const v2i o2 = {static_cast<int>(q.x), static_cast<int>(q.y)};
+  __builtin_amdgcn_raw_buffer_store_b64(o2, r, off, 0, AUX);
+}
 // (no early exit for the rows past the end: their buffers have 0-byte ranges, so every
 // access is a no-op, and the kernel-argument loads are not split by a branch into two
 // dependent rounds before the first global load)
@@ -75,12 +100,7 @@ __global__ __launch_bounds__(256) void add_rms_bf16_kernel(const NormParams p) {
   const auto wr = norm_row_rsrc(p.w, p.cols * 4);
   const auto orr = norm_row_rsrc(static_cast<bf16_t*>(p.out) + base, cb2);
   const auto ror = norm_row_rsrc(RO ? static_cast<float*>(p.res_out) + base : p.w, cb4);
-  typedef __attribute__((__vector_size__(4 * sizeof(float)))) float v4f;
-  auto off = [&](int j, int es) {
-    int o = lane * 4 + 256 * j < p.cols ? (lane * 4 + 256 * j) * es : kNormOut;
-    asm volatile("" : "+v"(o));  // a select, not a branch around the access
-    return o;
-  };
+  auto off = [&](int j, int es) { return norm_chunk_off(lane, j, p.cols, es); };
   uint32_t xq[CPL][2];
   v4f rq[CPL], wq[CPL];
 #pragma unroll
@@ -97,8 +117,7 @@ __global__ __launch_bounds__(256) void add_rms_bf16_kernel(const NormParams p) {
   float v[CPL][4];
 #pragma unroll
   for (int j = 0; j < CPL; ++j) {
-    v[j][0] = __uint_as_float(xq[j][0] << 16); v[j][1] = __uint_as_float(xq[j][0] & 0xffff0000u);
-    v[j][2] = __uint_as_float(xq[j][1] << 16); v[j][3] = __uint_as_float(xq[j][1] & 0xffff0000u);
+    unpack_bf16x4(xq[j][0], xq[j][1], v[j]);
     if constexpr (RES) {
 #pragma unroll
       for (int i = 0; i < 4; ++i) v[j][i] += rq[j][i];
@@ -116,12 +135,7 @@ __global__ __launch_bounds__(256) void add_rms_bf16_kernel(const NormParams p) {
     float y[4];
 #pragma unroll
     for (int i = 0; i < 4; ++i) y[i] = (v[j][i] - mean) * rstd * wq[j][i];
-    typedef __attribute__((__vector_size__(2 * sizeof(int)))) int v2i;
-    const v2i o2 = {static_cast<int>(static_cast<uint32_t>(from_f32<bf16_t>(y[0])) |
-                                     (static_cast<uint32_t>(from_f32<bf16_t>(y[1])) << 16)),
-                    static_cast<int>(static_cast<uint32_t>(from_f32<bf16_t>(y[2])) |
-                                     (static_cast<uint32_t>(from_f32<bf16_t>(y[3])) << 16))};
-    __builtin_amdgcn_raw_buffer_store_b64(o2, orr, off(j, 2), 0, ST);
+    store_bf16x4<ST>(y, orr, off(j, 2));
     if constexpr (RO) {
       typedef __attribute__((__vector_size__(4 * sizeof(int)))) int v4i;
       const v4i r4 = {static_cast<int>(__float_as_uint(v[j][0])), static_cast<int>(__float_as_uint(v[j][1])),
@@ -258,8 +272,6 @@ __global__ __launch_bounds__(256) void add_norm_kernel(const NormParams p) {
 // of the rounded outputs to part[b][g][slice].  pool_finish_kernel then sums the slices
 // (and groups) in a fixed order, so the result is deterministic and independent of the
 // launch geometry; the reference's means are of the rounded patch tokens as well.
-constexpr int kPoolRB = 16;
-constexpr bool kPoolFast = true;  // bf16 rows through norm_pool_rows_bf16_kernel
 
 struct NormPoolParams {
   const void* x; const void* res; const float* w; const float* bias; void* out;
@@ -272,6 +284,33 @@ struct NormPoolParams {
   int slices;                       // kPoolRB-row slices per group
   float* part;                      // (batch, groups, slices, cols) or nullptr
 };
+
+// Input row of output row r: frame-order reversal of the grouped rows (BiMamba backward).
+__device__ __forceinline__ int pool_in_row(const NormPoolParams& p, int r) {
+  if (p.rev_frame > 0 && r >= p.head) {
+    const int x = r - p.head, F = p.rev_frame;
+    return p.head + x + (p.rows - p.head - F) - 2 * F * (x / F);
+  }
+  return r;
+}
+
+// The four waves' column sums of slice s of group gy - 1, added in wave order into its part.
+template <int CPL>
+__device__ __forceinline__ void pool_store_part(const NormPoolParams& p, float* red,
+                                                const float (&acc)[CPL][4], int b, int gy, int s,
+                                                int wave, int lane) {
+#pragma unroll
+  for (int j = 0; j < CPL; ++j) {
+    const int c = lane * 4 + 256 * j;
+    if (c < p.cols)
+#pragma unroll
+      for (int i = 0; i < 4; ++i) red[wave * p.cols + c + i] = acc[j][i];
+  }
+  __syncthreads();
+  float* dst = p.part + (((long long)b * p.groups + gy - 1) * p.slices + s) * p.cols;
+  for (int c = threadIdx.x; c < p.cols; c += 256)
+    dst[c] = ((red[c] + red[p.cols + c]) + red[2 * p.cols + c]) + red[3 * p.cols + c];
+}
 
 template <int CPL>
 __global__ __launch_bounds__(256) void norm_pool_rows_kernel(const NormPoolParams p) {
@@ -298,11 +337,7 @@ __global__ __launch_bounds__(256) void norm_pool_rows_kernel(const NormPoolParam
 #pragma unroll
     for (int i = 0; i < 4; ++i) acc[j][i] = 0.0f;
   for (int r = r0 + wave; r < r1; r += 4) {
-    int ri = r;  // input row: frame-order reversal of the grouped rows (BiMamba backward)
-    if (p.rev_frame > 0 && r >= p.head) {
-      const int x = r - p.head, F = p.rev_frame;
-      ri = p.head + x + (p.rows - p.head - F) - 2 * F * (x / F);
-    }
+    const int ri = pool_in_row(p, r);
     const long long in = (long long)b * p.in_bstride + (long long)ri * p.cols;
     const long long on = (long long)b * p.out_bstride + (long long)r * p.cols;
     float v[CPL][4];
@@ -356,17 +391,7 @@ __global__ __launch_bounds__(256) void norm_pool_rows_kernel(const NormPoolParam
     }
   }
   if (gy == 0 || !p.part) return;
-#pragma unroll
-  for (int j = 0; j < CPL; ++j) {
-    const int c = lane * 4 + 256 * j;
-    if (c < p.cols)
-#pragma unroll
-      for (int i = 0; i < 4; ++i) red[wave * p.cols + c + i] = acc[j][i];
-  }
-  __syncthreads();
-  float* dst = p.part + (((long long)b * p.groups + gy - 1) * p.slices + s) * p.cols;
-  for (int c = threadIdx.x; c < p.cols; c += 256)
-    dst[c] = ((red[c] + red[p.cols + c]) + red[2 * p.cols + c]) + red[3 * p.cols + c];
+  pool_store_part<CPL>(p, red, acc, b, gy, s, wave, lane);
 }
 
 // norm_pool_rows_kernel for bf16 x / out with an fp32 (or no) residual: the same arithmetic
@@ -394,23 +419,14 @@ __global__ __launch_bounds__(256) void norm_pool_rows_bf16_kernel(const NormPool
   }
   const int r0 = lo + s * kPoolRB;
   const int r1 = min(hi, r0 + kPoolRB);
-  typedef __attribute__((__vector_size__(4 * sizeof(float)))) float v4f;
-  auto off = [&](int j, int es) {
-    int o = lane * 4 + 256 * j < p.cols ? (lane * 4 + 256 * j) * es : kNormOut;
-    asm volatile("" : "+v"(o));
-    return o;
-  };
+  auto off = [&](int j, int es) { return norm_chunk_off(lane, j, p.cols, es); };
   uint32_t xq[RPW][CPL][2];
   v4f rq[RPW][CPL];
 #pragma unroll
   for (int k = 0; k < RPW; ++k) {
     const int r = r0 + wave + 4 * k;
     const bool live = r < r1;
-    int ri = live ? r : 0;
-    if (p.rev_frame > 0 && ri >= p.head) {
-      const int x = ri - p.head, F = p.rev_frame;
-      ri = p.head + x + (p.rows - p.head - F) - 2 * F * (x / F);
-    }
+    const int ri = pool_in_row(p, live ? r : 0);
     const long long in = (long long)b * p.in_bstride + (long long)ri * p.cols;
     const auto xr = norm_row_rsrc(static_cast<const bf16_t*>(p.x) + in, live ? p.cols * 2 : 0);
     const auto rr = norm_row_rsrc(p.res ? static_cast<const float*>(p.res) + in : p.w,
@@ -439,8 +455,7 @@ __global__ __launch_bounds__(256) void norm_pool_rows_bf16_kernel(const NormPool
 #pragma unroll
     for (int j = 0; j < CPL; ++j) {
       const bool in_c = lane * 4 + 256 * j < p.cols;
-      v[j][0] = __uint_as_float(xq[k][j][0] << 16); v[j][1] = __uint_as_float(xq[k][j][0] & 0xffff0000u);
-      v[j][2] = __uint_as_float(xq[k][j][1] << 16); v[j][3] = __uint_as_float(xq[k][j][1] & 0xffff0000u);
+      unpack_bf16x4(xq[k][j][0], xq[k][j][1], v[j]);
       if (p.res) {
 #pragma unroll
         for (int i = 0; i < 4; ++i) v[j][i] += rq[k][j][i];
@@ -478,34 +493,17 @@ __global__ __launch_bounds__(256) void norm_pool_rows_bf16_kernel(const NormPool
           y[i] = to_f32(from_f32<bf16_t>(y[i]));
           acc[j][i] += y[i];
         }
-        typedef __attribute__((__vector_size__(2 * sizeof(int)))) int v2i;
-        const v2i o2 = {static_cast<int>(static_cast<uint32_t>(from_f32<bf16_t>(y[0])) |
-                                         (static_cast<uint32_t>(from_f32<bf16_t>(y[1])) << 16)),
-                        static_cast<int>(static_cast<uint32_t>(from_f32<bf16_t>(y[2])) |
-                                         (static_cast<uint32_t>(from_f32<bf16_t>(y[3])) << 16))};
-        __builtin_amdgcn_raw_buffer_store_b64(o2, orr, c * 2, 0, 0);
+        store_bf16x4<0>(y, orr, c * 2);
       }
     }
   }
   if (gy == 0 || !p.part) return;
-#pragma unroll
-  for (int j = 0; j < CPL; ++j) {
-    const int c = lane * 4 + 256 * j;
-    if (c < p.cols)
-#pragma unroll
-      for (int i = 0; i < 4; ++i) red[wave * p.cols + c + i] = acc[j][i];
-  }
-  __syncthreads();
-  float* dst = p.part + (((long long)b * p.groups + gy - 1) * p.slices + s) * p.cols;
-  for (int c = threadIdx.x; c < p.cols; c += 256)
-    dst[c] = ((red[c] + red[p.cols + c]) + red[2 * p.cols + c]) + red[3 * p.cols + c];
+  pool_store_part<CPL>(p, red, acc, b, gy, s, wave, lane);
 }
 
 // Pool finish: per (pooled row, batch row) sum the slices of its group(s) in order, take
 // the mean (rounded to the output dtype like the reference's bf16 mean), add the CLS row
 // for cls+avg, and apply the pool LayerNorm (fp32 statistics, eps of the module).
-enum PoolMode { kPoolAvg = 0, kPoolClsAvg = 1, kPoolClsCatAvg = 2, kPoolCls = 3 };
-
 struct PoolFinishParams {
   const float* part; int groups, slices, group_rows; const int* bounds;
   const void* cls; long long cls_bstride; int cls_dtype;
@@ -622,6 +620,58 @@ __global__ __launch_bounds__(1024) void pool_finish_kernel(const PoolFinishParam
   }
 }
 
+// ---------------------------------------------------------------------------------------
+// Host side.  vm_norm_plan.h decides the instance, the geometry and the workspace layout; an
+// entry builds the plan's input, turns a refusal into its message and launches what the plan
+// names.  The pickers' switches on the plan's fields name every instance there is.
+using NormKernel = void (*)(const NormParams);
+using NormPoolKernel = void (*)(const NormPoolParams);
+
+template <int CPL>
+static NormKernel add_rms_bf16_forms(const AddNormPlan& pl) {
+  switch (pl.write_through ? 4 : 2 * pl.res + pl.ro) {
+    case 0: return add_rms_bf16_kernel<CPL, false, false>;
+    case 1: return add_rms_bf16_kernel<CPL, false, true>;
+    case 2: return add_rms_bf16_kernel<CPL, true, false>;
+    case 3: return add_rms_bf16_kernel<CPL, true, true>;
+    default: return add_rms_bf16_kernel<CPL, true, true, kSmallStoreWT>;
+  }
+}
+static NormKernel add_norm_instance(const AddNormPlan& pl) {
+  switch (static_cast<int>(pl.family) * 100 + pl.cpl) {  // kFast 0, kVec 1, kScalar 2
+    case 1: return add_rms_bf16_forms<1>(pl);
+    case 2: return add_rms_bf16_forms<2>(pl);
+    case 3: return add_rms_bf16_forms<3>(pl);
+    case 4: return add_rms_bf16_forms<4>(pl);
+    case 101: return add_norm_vec_kernel<1>;
+    case 102: return add_norm_vec_kernel<2>;
+    case 104: return add_norm_vec_kernel<4>;
+    case 108: return add_norm_vec_kernel<8>;
+    case 204: return add_norm_kernel<4>;
+    case 208: return add_norm_kernel<8>;
+    case 216: return add_norm_kernel<16>;
+    default: return add_norm_kernel<32>;
+  }
+}
+static NormPoolKernel norm_pool_instance(const NormPoolPlan& pl) {
+  switch ((pl.family == NormFamily::kFast ? 0 : 100) + pl.cpl) {
+    case 1: return norm_pool_rows_bf16_kernel<1>;
+    case 2: return norm_pool_rows_bf16_kernel<2>;
+    case 3: return norm_pool_rows_bf16_kernel<3>;
+    case 4: return norm_pool_rows_bf16_kernel<4>;
+    case 101: return norm_pool_rows_kernel<1>;
+    case 102: return norm_pool_rows_kernel<2>;
+    case 104: return norm_pool_rows_kernel<4>;
+    default: return norm_pool_rows_kernel<8>;
+  }
+}
+
+// A refusal: the entry's message for kNull, kShape, kAlign, kWorkspace in that order.
+static int norm_refuse(NormWhy why, const char* const (&msg)[4]) {
+  vmhost::set_error("%s", msg[static_cast<int>(why) - 1]);
+  return VM_E_INVALID;
+}
+
 }  // namespace vm
 
 using namespace vm;
@@ -629,8 +679,7 @@ using namespace vm;
 extern "C" long long vm_norm_pool_workspace_bytes(int batch, int groups, int max_group_rows,
                                                   int cols) {
   if (batch < 0 || groups < 0 || max_group_rows < 0 || cols < 0) return -1;
-  const long long slices = (max_group_rows + kPoolRB - 1) / kPoolRB;
-  return (long long)batch * groups * slices * cols * static_cast<long long>(sizeof(float));
+  return plan_norm_pool_shape(batch, groups, max_group_rows, cols).workspace_bytes;
 }
 
 extern "C" int vm_norm_pool_fwd(const void* x, int x_dtype, const void* residual, int res_dtype,
@@ -640,58 +689,35 @@ extern "C" int vm_norm_pool_fwd(const void* x, int x_dtype, const void* residual
                                 int head, int groups, int group_rows, const int* bounds,
                                 int max_group_rows, int rev_frame, void* workspace,
                                 long long workspace_bytes, vm_stream_t stream) {
-  if (!x || !weight || !out) {
-    vmhost::set_error("vm_norm_pool_fwd: null required pointer");
-    return VM_E_INVALID;
-  }
-  if (batch < 0 || rows < 0 || cols < 4 || cols > 2048 || cols % 4 || head < 0 || head > rows ||
-      groups < 1 || max_group_rows < 0 || in_batch_stride < (long long)rows * cols ||
-      in_batch_stride % 4 || out_batch_stride < (long long)rows * cols || out_batch_stride % 4 ||
-      rev_frame < 0 || (rev_frame > 0 && (rows - head) % rev_frame) ||
-      !vmhost::dtype_ok(x_dtype) || !vmhost::dtype_ok(out_dtype) ||
-      (residual && !vmhost::dtype_ok(res_dtype)) ||
-      (!bounds && head + (long long)groups * group_rows != rows) ||
-      (!bounds && group_rows != max_group_rows)) {
-    vmhost::set_error("vm_norm_pool_fwd: bad shape/dtype (cols % 4 == 0, cols <= 2048; "
-                      "implicit groups must tile rows after the head)");
-    return VM_E_INVALID;
-  }
-  if (!vmhost::aligned16(x) || !vmhost::aligned16(out) || !vmhost::aligned16(weight) ||
-      (residual && !vmhost::aligned16(residual))) {
-    vmhost::set_error("vm_norm_pool_fwd: x, residual, out and weight must be 16-byte aligned");
-    return VM_E_INVALID;
-  }
-  const long long need = vm_norm_pool_workspace_bytes(batch, groups, max_group_rows, cols);
-  if (workspace && workspace_bytes < need) {
-    vmhost::set_error("vm_norm_pool_fwd: workspace smaller than vm_norm_pool_workspace_bytes");
-    return VM_E_INVALID;
-  }
-  if (batch == 0 || rows == 0) return VM_OK;
+  static const char* const kWhy[4] = {
+      "vm_norm_pool_fwd: null required pointer",
+      "vm_norm_pool_fwd: bad shape/dtype (cols % 4 == 0, cols <= 2048; "
+      "implicit groups must tile rows after the head)",
+      "vm_norm_pool_fwd: x, residual, out and weight must be 16-byte aligned",
+      "vm_norm_pool_fwd: workspace smaller than vm_norm_pool_workspace_bytes"};
+  NormPoolPlanIn in{};
+  in.batch = batch; in.rows = rows; in.cols = cols; in.head = head; in.groups = groups;
+  in.group_rows = group_rows; in.max_group_rows = max_group_rows; in.rev_frame = rev_frame;
+  in.in_bstride = in_batch_stride; in.out_bstride = out_batch_stride;
+  in.has_x = x; in.has_weight = weight; in.has_out = out;
+  in.has_res = residual; in.has_bounds = bounds; in.has_ws = workspace;
+  in.x_dtype = x_dtype; in.res_dtype = res_dtype; in.out_dtype = out_dtype;
+  in.x_al = vmhost::aligned16(x); in.res_al = vmhost::aligned16(residual);
+  in.w_al = vmhost::aligned16(weight); in.out_al = vmhost::aligned16(out);
+  in.workspace_bytes = workspace_bytes;
+  const NormPoolPlan pl = plan_norm_pool(in);
+  if (pl.why != NormWhy::kOk) return norm_refuse(pl.why, kWhy);
+  if (pl.empty) return VM_OK;
   NormPoolParams p{};
   p.x = x; p.res = residual; p.w = weight; p.bias = bias; p.out = out;
   p.in_bstride = in_batch_stride; p.out_bstride = out_batch_stride; p.rev_frame = rev_frame;
   p.rows = rows; p.cols = cols; p.eps = eps; p.is_rms = is_rms;
   p.x_dtype = x_dtype; p.res_dtype = res_dtype; p.out_dtype = out_dtype;
   p.head = head; p.groups = groups; p.group_rows = group_rows; p.bounds = bounds;
-  p.slices = max_group_rows > 0 ? (max_group_rows + kPoolRB - 1) / kPoolRB : 1;
+  p.slices = pl.slices;
   p.part = static_cast<float*>(workspace);
-  // x: the kPoolRB-row slices of a group, or of the head rows where those are more
-  dim3 grid(std::max(p.slices, (head + kPoolRB - 1) / kPoolRB), groups + 1, batch);
-  const size_t lds = 4 * cols * sizeof(float);
-  hipStream_t s = static_cast<hipStream_t>(stream);
-  const int cpl = (cols + 255) / 256;
-  const bool fast = kPoolFast && x_dtype == VM_DTYPE_BF16 && out_dtype == VM_DTYPE_BF16 &&
-                    (!residual || res_dtype == VM_DTYPE_F32) && cpl <= 4 &&
-                    (long long)(rows + 1) * cols * 4 < (1ll << 31);
-  if (fast) {
-    if (cpl <= 1) hipLaunchKernelGGL(norm_pool_rows_bf16_kernel<1>, grid, dim3(256), lds, s, p);
-    else if (cpl <= 2) hipLaunchKernelGGL(norm_pool_rows_bf16_kernel<2>, grid, dim3(256), lds, s, p);
-    else if (cpl <= 3) hipLaunchKernelGGL(norm_pool_rows_bf16_kernel<3>, grid, dim3(256), lds, s, p);
-    else hipLaunchKernelGGL(norm_pool_rows_bf16_kernel<4>, grid, dim3(256), lds, s, p);
-  } else if (cpl <= 1) hipLaunchKernelGGL(norm_pool_rows_kernel<1>, grid, dim3(256), lds, s, p);
-  else if (cpl <= 2) hipLaunchKernelGGL(norm_pool_rows_kernel<2>, grid, dim3(256), lds, s, p);
-  else if (cpl <= 4) hipLaunchKernelGGL(norm_pool_rows_kernel<4>, grid, dim3(256), lds, s, p);
-  else hipLaunchKernelGGL(norm_pool_rows_kernel<8>, grid, dim3(256), lds, s, p);
+  hipLaunchKernelGGL(norm_pool_instance(pl), dim3(pl.gx, pl.gy, pl.gz), dim3(pl.block), pl.lds,
+                     static_cast<hipStream_t>(stream), p);
   return vmhost::launch_status("vm_norm_pool_fwd");
 }
 
@@ -701,27 +727,24 @@ extern "C" int vm_pool_finish_fwd(const void* workspace, int batch, int groups, 
                                   int keep_temporal, const float* ln_weight, const float* ln_bias,
                                   float ln_eps, void* x_pool, int xp_dtype, int cols,
                                   vm_stream_t stream) {
-  const bool needs_cls = mode == kPoolClsAvg || mode == kPoolClsCatAvg || mode == kPoolCls;
-  const bool needs_avg = mode != kPoolCls;
-  if (!x_pool || (needs_cls && !cls) || (needs_avg && !workspace)) {
-    vmhost::set_error("vm_pool_finish_fwd: null required pointer");
-    return VM_E_INVALID;
-  }
-  if (batch < 0 || groups < 1 || mode < 0 || mode > 3 || cols < 4 || cols > 2048 || cols % 4 ||
-      max_group_rows < 1 || !vmhost::dtype_ok(xp_dtype) || (cls && !vmhost::dtype_ok(cls_dtype))) {
-    vmhost::set_error("vm_pool_finish_fwd: bad mode/shape/dtype");
-    return VM_E_INVALID;
-  }
-  if (batch == 0) return VM_OK;
+  static const char* const kWhy[4] = {"vm_pool_finish_fwd: null required pointer",
+                                      "vm_pool_finish_fwd: bad mode/shape/dtype"};
+  PoolFinishPlanIn in{};
+  in.batch = batch; in.groups = groups; in.max_group_rows = max_group_rows; in.cols = cols;
+  in.mode = mode; in.keep_temporal = keep_temporal;
+  in.has_ws = workspace; in.has_cls = cls; in.has_xpool = x_pool;
+  in.cls_dtype = cls_dtype; in.xp_dtype = xp_dtype;
+  const PoolFinishPlan pl = plan_pool_finish(in);
+  if (pl.why != NormWhy::kOk) return norm_refuse(pl.why, kWhy);
+  if (pl.empty) return VM_OK;
   PoolFinishParams p{};
   p.part = static_cast<const float*>(workspace); p.groups = groups;
-  p.slices = (max_group_rows + kPoolRB - 1) / kPoolRB; p.group_rows = group_rows;
+  p.slices = pl.slices; p.group_rows = group_rows;
   p.bounds = bounds; p.cls = cls; p.cls_bstride = cls_batch_stride; p.cls_dtype = cls_dtype;
   p.mode = mode; p.keep_temporal = keep_temporal; p.lnw = ln_weight; p.lnb = ln_bias;
   p.ln_eps = ln_eps; p.xpool = x_pool; p.xp_dtype = xp_dtype; p.cols = cols;
-  const int navg = keep_temporal ? groups : 1;
-  p.prow = mode == kPoolCls ? 1 : (mode == kPoolClsCatAvg ? 1 + navg : navg);
-  hipLaunchKernelGGL(pool_finish_kernel, dim3(p.prow, batch), dim3(1024), 0,
+  p.prow = pl.prow;
+  hipLaunchKernelGGL(pool_finish_kernel, dim3(pl.gx, pl.gy), dim3(pl.block), 0,
                      static_cast<hipStream_t>(stream), p);
   return vmhost::launch_status("vm_pool_finish_fwd");
 }
@@ -730,62 +753,26 @@ extern "C" int vm_add_norm_fwd(const void* x, int x_dtype, const void* residual,
                                const float* weight, const float* bias, void* out, int out_dtype,
                                void* residual_out, int res_out_dtype, long long rows, int cols,
                                float eps, int is_rms, vm_stream_t stream) {
-  if (!x || !weight || !out) {
-    vmhost::set_error("vm_add_norm_fwd: null required pointer");
-    return VM_E_INVALID;
-  }
-  if (rows < 0 || cols < 1 || cols > 64 * 32 || !vmhost::dtype_ok(x_dtype) ||
-      !vmhost::dtype_ok(out_dtype) || (residual && !vmhost::dtype_ok(res_dtype)) ||
-      (residual_out && !vmhost::dtype_ok(res_out_dtype))) {
-    vmhost::set_error("vm_add_norm_fwd: bad shape/dtype (cols must be in [1, 2048])");
-    return VM_E_INVALID;
-  }
-  if (rows == 0) return VM_OK;
+  static const char* const kWhy[4] = {
+      "vm_add_norm_fwd: null required pointer",
+      "vm_add_norm_fwd: bad shape/dtype (cols must be in [1, 2048])"};
+  AddNormPlanIn in{};
+  in.rows = rows; in.cols = cols; in.is_rms = is_rms;
+  in.has_x = x; in.has_weight = weight; in.has_out = out;
+  in.has_bias = bias; in.has_res = residual; in.has_ro = residual_out;
+  in.x_dtype = x_dtype; in.res_dtype = res_dtype; in.out_dtype = out_dtype;
+  in.ro_dtype = res_out_dtype;
+  in.x_al = vmhost::aligned16(x); in.res_al = vmhost::aligned16(residual);
+  in.w_al = vmhost::aligned16(weight); in.out_al = vmhost::aligned16(out);
+  in.ro_al = vmhost::aligned16(residual_out);
+  const AddNormPlan pl = plan_add_norm(in);
+  if (pl.why != NormWhy::kOk) return norm_refuse(pl.why, kWhy);
+  if (pl.empty) return VM_OK;
   NormParams p{};
   p.x = x; p.res = residual; p.w = weight; p.bias = bias; p.out = out; p.res_out = residual_out;
   p.rows = rows; p.cols = cols; p.eps = eps; p.is_rms = is_rms;
   p.x_dtype = x_dtype; p.res_dtype = res_dtype; p.out_dtype = out_dtype; p.ro_dtype = res_out_dtype;
-  dim3 grid(static_cast<unsigned>((rows + 3) / 4));
-  hipStream_t s = static_cast<hipStream_t>(stream);
-  const bool vec = cols % 4 == 0 && vmhost::aligned16(x) && vmhost::aligned16(out) &&
-                   vmhost::aligned16(weight) && (!residual || vmhost::aligned16(residual)) &&
-                   (!residual_out || vmhost::aligned16(residual_out));
-  if (vec && is_rms && !bias && x_dtype == VM_DTYPE_BF16 && out_dtype == VM_DTYPE_BF16 &&
-      (!residual || res_dtype == VM_DTYPE_F32) && (!residual_out || res_out_dtype == VM_DTYPE_F32) &&
-      cols <= 256 * 4) {
-    const int cpl = (cols + 255) / 256;
-    // streaming-chunk row counts: the stores write through (kSmallStoreWT)
-    const bool wt = rows <= kSmallStoreRows;
-#define VM_RMS_BF16(CPLV)                                                                   \
-  if (residual && residual_out && wt)                                                       \
-    hipLaunchKernelGGL((add_rms_bf16_kernel<CPLV, true, true, kSmallStoreWT>), grid, dim3(256), 0, s, p); \
-  else if (residual && residual_out)                                                        \
-    hipLaunchKernelGGL((add_rms_bf16_kernel<CPLV, true, true>), grid, dim3(256), 0, s, p);   \
-  else if (residual)                                                                        \
-    hipLaunchKernelGGL((add_rms_bf16_kernel<CPLV, true, false>), grid, dim3(256), 0, s, p);  \
-  else if (residual_out)                                                                    \
-    hipLaunchKernelGGL((add_rms_bf16_kernel<CPLV, false, true>), grid, dim3(256), 0, s, p);  \
-  else                                                                                      \
-    hipLaunchKernelGGL((add_rms_bf16_kernel<CPLV, false, false>), grid, dim3(256), 0, s, p);
-    if (cpl <= 1) { VM_RMS_BF16(1) }
-    else if (cpl <= 2) { VM_RMS_BF16(2) }
-    else if (cpl <= 3) { VM_RMS_BF16(3) }
-    else { VM_RMS_BF16(4) }
-#undef VM_RMS_BF16
-    return vmhost::launch_status("vm_add_norm_fwd");
-  }
-  if (vec) {
-    const int cpl = (cols + 255) / 256;
-    if (cpl <= 1) hipLaunchKernelGGL(add_norm_vec_kernel<1>, grid, dim3(256), 0, s, p);
-    else if (cpl <= 2) hipLaunchKernelGGL(add_norm_vec_kernel<2>, grid, dim3(256), 0, s, p);
-    else if (cpl <= 4) hipLaunchKernelGGL(add_norm_vec_kernel<4>, grid, dim3(256), 0, s, p);
-    else hipLaunchKernelGGL(add_norm_vec_kernel<8>, grid, dim3(256), 0, s, p);
-    return vmhost::launch_status("vm_add_norm_fwd");
-  }
-  const int vpl = (cols + 63) / 64;
-  if (vpl <= 4) hipLaunchKernelGGL(add_norm_kernel<4>, grid, dim3(256), 0, s, p);
-  else if (vpl <= 8) hipLaunchKernelGGL(add_norm_kernel<8>, grid, dim3(256), 0, s, p);
-  else if (vpl <= 16) hipLaunchKernelGGL(add_norm_kernel<16>, grid, dim3(256), 0, s, p);
-  else hipLaunchKernelGGL(add_norm_kernel<32>, grid, dim3(256), 0, s, p);
+  hipLaunchKernelGGL(add_norm_instance(pl), dim3(pl.grid), dim3(pl.block), 0,
+                     static_cast<hipStream_t>(stream), p);
   return vmhost::launch_status("vm_add_norm_fwd");
 }
